@@ -23,12 +23,20 @@ status.  The process group is gloo: ranks only meet at the timing barriers,
 the max-over-ranks reduction and, after timing, the parity gather of
 per-block digests -- no data-path collective, no RCCL.
 
-Extra JSON fields: per-kernel HIP-event timings (``kernels``), the roofline
-of the dominant kernel (algorithmic bytes = raw + compressed + 16 per block,
-SURVEY §8d), the CPU baseline (the reference snappy.c from oracle/_ref, rank 0
-at N = 1 only, BASELINE.md's plan: 1 thread and the host's thread share, same
-blocks, median of 5) and the parity of this run's output against the
-reference digests.
+A plain run sets up, warms up, times the K steps and prints the result line:
+``value``, ``ms_per_step``, and what the timed steps' own HIP events give for
+free (``kernels``, ``encode_GiBps`` / ``decode_GiBps``, the roofline of the
+dominant kernel: algorithmic bytes = raw + compressed + 16 per block, SURVEY
+§8d).  ``--dump-outputs DIR`` also writes what the last timed step computed
+(dump_outputs below), so two builds can be compared output for output.
+
+``--full`` adds every leg that takes runs of its own (each can be switched
+off with its ``--no-...`` option): the parity of this run's output against
+the reference digests, the concurrent encode || decode measurement, the 1 GiB
+copy probe behind ``roofline.achievable_copy_GBps``, the CPU baseline (the
+reference snappy.c from oracle/_ref, rank 0 at N = 1 only, BASELINE.md's plan:
+1 thread and the host's thread share, same blocks, median of 5), the batched
+table paths and C3.  Without ``--full`` those fields are null.
 """
 from __future__ import annotations
 
@@ -62,6 +70,12 @@ def parse(argv=None) -> argparse.Namespace:
     p.add_argument("--block-size", type=int, default=4096)
     p.add_argument("--copies", type=int, default=2,
                    help="independent corpus copies rotated per step (defeats the 256 MiB MALL)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs beyond the headline figure: parity against the "
+                        "reference digests, pipelined encode||decode, copy probe, CPU "
+                        "baseline, table paths, C3 (each has its own --no-... switch)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as DIR/<name>.npy (float32)")
     p.add_argument("--cpu-reps", type=int, default=5)
     p.add_argument("--cpu-threads", type=int, default=0,
                    help="the multi-thread CPU point (0: this host's CPU share, <= 16)")
@@ -83,7 +97,12 @@ def parse(argv=None) -> argparse.Namespace:
                    help="no GPU: launch, partition and digest-gather only (CPU tests)")
     p.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
                    help="PMC traffic summary (tools/traffic_json.py)")
-    return p.parse_args(argv)
+    a = p.parse_args(argv)
+    if not a.full:
+        # a plain run does only what `value` needs
+        a.no_cpu_baseline = a.no_parity = a.no_copy_probe = True
+        a.no_pipelined = a.no_table = a.no_c3 = True
+    return a
 
 
 def total_blocks(a, world: int) -> int:
@@ -187,6 +206,8 @@ def main(argv=None) -> int:
     a = parse(argv)
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         return spawn_ranks(a.gpus, argv)
     rank = int(os.environ.get("RANK", "0"))
@@ -277,6 +298,10 @@ def run(a, rank: int, world: int, local: int, dist) -> None:
     if dist:
         per_rank = [None] * world
         dist.all_gather_object(per_rank, t1 - t0)
+
+    if a.dump_outputs:
+        j = (a.steps - 1) % a.copies              # the copy the last timed step worked on
+        dump_outputs(a.dump_outputs, comps[j], outs[j], stats[j], rank, world)
 
     # ---- extra (not `value`): encode and decode concurrently on two streams,
     # step k encoding copy k while decoding what step k-1 encoded -- the shape
@@ -474,6 +499,46 @@ def run(a, rank: int, world: int, local: int, dist) -> None:
             "gen_seconds": t_gen,
         }
         print(json.dumps(line), flush=True)
+
+
+DUMP_SAMPLE, DUMP_SEED, DUMP_BUDGET = 1024, 0x5EED, 48 << 20
+
+
+def dump_outputs(path: str, comp, out, status, rank: int, world: int) -> None:
+    """What a caller of one step (batch.encode, then batch.decode) receives,
+    as float32 .npy files in `path` (every value is a byte, a length below
+    2^24 or a status: exact in float32):
+
+      comp_len, decoded_len, status   one value per block, every block
+      sample_index                    the blocks whose bytes are written: a
+                                      fixed, seeded choice of DUMP_SAMPLE
+                                      blocks (fewer if there are fewer, or
+                                      wider ones), ascending
+      comp_bytes, decoded_bytes       (sample, widest slot) the used bytes of
+                                      each sampled block, zero-padded
+
+    The byte arrays together stay under DUMP_BUDGET.  The sample is gathered
+    on the device; at N > 1 each rank writes its shard as <name>_rank<r>.npy."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n = comp.n
+    per_block = 4 * (comp.max_cap + out.max_cap)
+    m = max(1, min(n, DUMP_SAMPLE, DUMP_BUDGET // max(per_block, 1)))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=m, replace=False))
+    d_idx = torch.from_numpy(idx).to(comp.buf.device)
+
+    def gather(s) -> np.ndarray:
+        col = torch.arange(s.max_cap, device=s.buf.device, dtype=torch.int64)
+        pos = (s.off[d_idx].unsqueeze(1) + col).clamp_(max=s.buf.numel() - 1)
+        used = col.unsqueeze(0) < s.len[d_idx].unsqueeze(1)
+        return torch.where(used, s.buf[pos], 0).to(torch.float32).cpu().numpy()
+
+    arrays = {"comp_len": comp.len.cpu().numpy(), "decoded_len": out.len.cpu().numpy(),
+              "status": status.cpu().numpy(), "sample_index": idx,
+              "comp_bytes": gather(comp), "decoded_bytes": gather(out)}
+    tag = "" if world == 1 else f"_rank{rank}"
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, f"{name}{tag}.npy"), arr.astype(np.float32))
 
 
 def table_paths(c, raw, stream, enc_ms: float, dec_ms: float) -> dict:

@@ -181,13 +181,79 @@ def test_cpu_baseline_fields_on_cpu():
         assert set(cb["nproc"]["by_partition"]) == {"round-robin", "contiguous"}
 
 
+def _dumped_blocks(rows, lens) -> list[bytes]:
+    """The used bytes of each dumped row; the padding must be zero."""
+    import numpy as np
+    assert all(not row[int(k):].any() for row, k in zip(rows, lens))
+    return [row[:int(k)].astype(np.uint8).tobytes() for row, k in zip(rows, lens)]
+
+
+def test_dump_outputs_on_cpu(tmp_path):
+    """bench.py's dump_outputs on host tensors: lengths and statuses of every
+    block, the bytes of a fixed sample, all float32, the same from call to
+    call."""
+    import numpy as np
+    import torch
+
+    import bench
+    from lcdb_amd import batch, corpus
+    c = corpus.concat(corpus.fillseq(1100), corpus.random_blocks(5, 5000))
+    out, ooff, olen = oracle.best().encode_batch(c.buf, c.off, c.len, 1)
+    comp = batch.upload(corpus.Corpus(out, ooff.astype(np.uint64), olen.astype(np.uint32)), "cpu")
+    raw = batch.upload(c, "cpu")
+    st = torch.ones(c.n, dtype=torch.uint8)
+    got = []
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d), comp, raw, st, 0, 1)
+        got.append({p.stem: np.load(p) for p in sorted(d.iterdir())})
+    a, b = got
+    assert set(a) == {"comp_len", "decoded_len", "status", "sample_index", "comp_bytes",
+                      "decoded_bytes"}
+    assert all(v.dtype == np.float32 and np.array_equal(v, b[k]) for k, v in a.items())
+    assert sum(v.nbytes for v in a.values()) <= 64 * 10**6
+    idx = a["sample_index"].astype(int)
+    assert len(idx) == bench.DUMP_SAMPLE and (np.diff(idx) > 0).all() and idx[-1] < c.n
+    assert np.array_equal(a["comp_len"], olen) and np.array_equal(a["decoded_len"], c.len)
+    assert (a["status"] == 1).all()
+    hc = corpus.Corpus(out, ooff, olen)
+    assert _dumped_blocks(a["comp_bytes"], olen[idx]) == [hc.block(i) for i in idx]
+    assert _dumped_blocks(a["decoded_bytes"], c.len[idx]) == [c.block(i) for i in idx]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_its_last_step(digests, tmp_path):
+    """A plain bench.py run (no --full) only times its steps: the legs with
+    runs of their own stay null, --steps is the number of timed steps, and
+    --dump-outputs writes what the last step computed -- here all 1024 blocks
+    of C1, whose compressed bytes hash to the pinned reference digest."""
+    import numpy as np
+
+    from lcdb_amd import corpus
+    r = _bench("--gpus", "1", "--total-blocks", "1024", "--steps", "3", "--warmup", "1",
+               "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = _last_json(r.stdout)
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert line["value"] > 0 and line["unit"] == "GiB/s" and line["higher_is_better"] is True
+    assert all(line[k] is None for k in ("parity", "pipelined", "c3", "table", "cpu_baseline"))
+    a = {p.stem: np.load(p) for p in tmp_path.iterdir()}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert np.array_equal(a["sample_index"], np.arange(1024)) and (a["status"] == 1).all()
+    d = digests["C1_fillseq_1024x4KiB"]
+    comp = b"".join(_dumped_blocks(a["comp_bytes"], a["comp_len"]))
+    assert (hashlib.sha256(comp).hexdigest(), len(comp)) == (d["comp_sha256"], d["comp_bytes"])
+    c = corpus.fillseq(1024)
+    assert np.array_equal(a["decoded_len"], c.len)
+    assert _dumped_blocks(a["decoded_bytes"], a["decoded_len"]) == c.blocks()
+
+
 @pytest.mark.gpu
 def test_bench_two_ranks_on_the_gpu_c2(digests):
     """bench.py --gpus 2 on the GPU box (the ranks share its GPU): C2's 65 536
     blocks dealt g -> g % 2, every rank encodes and decodes its shard, and
     rank 0's re-interleaved per-block digests equal the pinned C2 comp_dd."""
     r = _bench("--gpus", "2", "--total-blocks", "65536", "--steps", "2", "--warmup", "1",
-               "--no-c3", "--no-cpu-baseline", "--no-pipelined", "--no-copy-probe")
+               "--full", "--no-c3", "--no-cpu-baseline", "--no-pipelined", "--no-copy-probe")
     assert r.returncode == 0, r.stderr[-3000:]
     line = _last_json(r.stdout)
     assert line["n_gpus"] == 2 and line["config"]["blocks_rank0"] == 32768
@@ -200,7 +266,7 @@ def test_bench_c4_full_stream_on_one_gpu(digests):
     """C4 (BASELINE.json configs[3]): the whole 1 048 576-block stream encoded
     and decoded on one GPU; compressed blocks equal the pinned C4 comp_dd."""
     r = _bench("--gpus", "1", "--total-blocks", "1048576", "--steps", "1", "--warmup", "1",
-               "--copies", "1", "--no-c3", "--no-cpu-baseline", "--no-pipelined",
+               "--copies", "1", "--full", "--no-c3", "--no-cpu-baseline", "--no-pipelined",
                "--no-copy-probe")
     assert r.returncode == 0, r.stderr[-3000:]
     line = _last_json(r.stdout)

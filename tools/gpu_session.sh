@@ -8,7 +8,7 @@
 #   tests     the whole -m gpu suite (K="-k expr" narrows it)
 #   service   the service / drop-in / lcdb-integration tests only
 #   smoke     __graft_entry__.smoke()
-#   bench     python bench.py (BENCH_ARGS)
+#   bench     python bench.py (BENCH_ARGS, default --full: every leg)
 #   rocprof   rocprofv3 --kernel-trace --stats of the bench's codec kernels
 #   pmc       PMC passes of the codec kernels (tools/profile.sh, PASSES)
 #   table     rocprofv3 summary of the table kernels (tools/bench_table.py)
@@ -37,6 +37,7 @@ want service && step service 600 gpurun_out/${P}_pytest_service.txt $T -m gpu \
 want smoke && step smoke 300 gpurun_out/${P}_smoke.log python -c "import __graft_entry__ as g; g.smoke()"
 if want bench; then
   echo "== bench"
+  BENCH_ARGS=${BENCH_ARGS:---full}
   timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > gpurun_out/${P}_bench.json 2> gpurun_out/${P}_bench.err \
     || { tail -5 gpurun_out/${P}_bench.err; exit 1; }
   grep '^{' gpurun_out/${P}_bench.json | tail -1 | head -c 600; echo
