@@ -302,6 +302,94 @@ int lgs_filter_block_match_host(const uint8_t *block, size_t block_len,
                                 const uint64_t *key_off, const uint32_t *key_len, uint32_t nq,
                                 int internal_keys, uint8_t *match);
 
+/* ---- building tables from sorted entries ----
+ *
+ * The data blocks lcdb's table builder makes from n entries in key order:
+ * ldb_tablegen_add (table_builder.c:215-255) appends each entry with
+ * ldb_blockgen_add (block_builder.c:91-136: shared | non_shared | value_size
+ * varint32s, the key's unshared bytes, the value; shared = 0 at every
+ * restart_interval-th entry of a block), and flushes the block through
+ * ldb_blockgen_finish (:138-151: the restart offsets and their count) as soon
+ * as ldb_blockgen_size_estimate (:153-158) reaches block_size
+ * (table_builder.c:251-254).  Entry i has key d_keys[d_key_off[i] ..
+ * + d_key_len[i]) and value d_vals[d_val_off[i] .. + d_val_len[i]); both
+ * buffers must stay readable 16 bytes past their end.
+ *
+ * Results: block b holds entries [d_block_first[b], d_block_first[b+1]) and
+ * is the d_raw_len[b] bytes at d_raw + d_raw_off[b], blocks packed one after
+ * the other -- the input lgs_table_write_dev takes; its index key (what the
+ * builder adds to the index block, table_builder.c:229-239, 332-341) is
+ * d_ikey[d_ikey_off[b] .. d_ikey_off[b+1]): the comparator's shortest
+ * separator of block b's last key and block b+1's first, its short successor
+ * of the last key for the last block.  internal_keys = 0: lcdb's bytewise
+ * comparator (comparator.c:44-88); 1: the DB's internal-key comparator
+ * (dbformat.c:232-285), which shortens the user key (all but the last 8
+ * bytes) and appends the fixed64 pack_seqtype(LDB_MAX_SEQUENCE,
+ * LDB_VALTYPE_SEEK) only when that user key got physically shorter.
+ *
+ * Limits: n < 2^31; every key + value under 2^30 bytes; every finished block
+ * under 2^31; restart_interval >= 1; with internal_keys every key has at
+ * least 8 bytes; keys strictly increase under the comparator, as lcdb
+ * asserts (block_builder.c:102-103) -- not checked.  The _host calls check
+ * the others (LGS_EINVAL) before any device work; they are the _dev caller's
+ * contract.  n = 0 yields no block.
+ *
+ * Two device calls, because the host needs the block count between them to
+ * size what follows.  lgs_block_cut_dev finds the blocks: it writes
+ * d_block_first, d_raw_off and d_ikey_off (room for n + 1 values each; entry
+ * [blocks] of the offsets is the total), d_raw_len (n) and d_counts[4] =
+ * {blocks, bytes of all raw blocks, longest block, bytes of all index keys}.
+ * lgs_block_emit_dev then writes the blocks into d_raw (d_counts[1] + 16
+ * bytes; lgs_block_build_bound(n, key bytes, value bytes) always suffices)
+ * and, unless d_ikey is NULL, the index keys into d_ikey (d_counts[3] bytes,
+ * at most the keys' total).  Both take the same lgs_block_build_scratch(n)
+ * bytes of device scratch, which must be left alone between them, and both
+ * are asynchronous on `stream`. */
+size_t lgs_block_build_bound(uint32_t n, uint64_t key_bytes, uint64_t value_bytes);
+size_t lgs_block_build_scratch(uint32_t n);
+int lgs_block_cut_dev(const uint8_t *d_keys, const uint64_t *d_key_off,
+                      const uint32_t *d_key_len, const uint32_t *d_val_len, uint32_t n,
+                      uint64_t block_size, uint32_t restart_interval, int internal_keys,
+                      uint32_t *d_block_first, uint64_t *d_raw_off, uint32_t *d_raw_len,
+                      uint64_t *d_ikey_off, uint64_t *d_counts, void *d_scratch,
+                      size_t scratch_bytes, void *stream);
+int lgs_block_emit_dev(const uint8_t *d_keys, const uint64_t *d_key_off,
+                       const uint32_t *d_key_len, const uint8_t *d_vals,
+                       const uint64_t *d_val_off, const uint32_t *d_val_len, uint32_t n,
+                       uint32_t restart_interval, int internal_keys, uint32_t nblocks,
+                       const uint32_t *d_block_first, const uint64_t *d_raw_off,
+                       const uint32_t *d_raw_len, uint8_t *d_raw, const uint64_t *d_ikey_off,
+                       uint8_t *d_ikey, void *d_scratch, size_t scratch_bytes, void *stream);
+/* Host arrays in and out (a pooled context, one synchronisation between cut
+   and emit).  raw_off, block_first and ikey_off need n + 1 entries, raw_len
+   n; LGS_ENOSPC when raw_cap or ikey_cap is too small. */
+int lgs_block_build_host(const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
+                         const uint8_t *vals, const uint64_t *val_off, const uint32_t *val_len,
+                         uint32_t n, uint64_t block_size, uint32_t restart_interval,
+                         int internal_keys, uint8_t *raw, size_t raw_cap, uint64_t *raw_off,
+                         uint32_t *raw_len, uint32_t *block_first, uint8_t *ikey,
+                         size_t ikey_cap, uint64_t *ikey_off, uint32_t *nblocks);
+
+/* The whole .ldb that ldb_tablegen_add for every entry and ldb_tablegen_finish
+   write (table_builder.c:215-365), byte for byte: the data blocks above
+   framed as lgs_table_write_dev frames them; with bits_per_key > 0 the filter
+   block of lgs_filter_block_build_dev, stored raw (:292-299); the metaindex
+   block (:301-328: the entry "filter.leveldb.BuiltinBloomFilter2" -> the
+   filter's handle, or no entry); the index block (:330-344: index key ->
+   ldb_handle_export of the block's handle, restart interval 1, :87), built by
+   the block builder itself; the 48-byte footer (format.c:92-106).  Everything
+   that grows with the table stays on the device until the one download of
+   the image; metaindex and footer are assembled on the host.  No entries
+   gives lcdb's empty table.  file_cap: lgs_table_build_bound(...) always
+   suffices; LGS_ENOSPC (with *file_size set when it is known) otherwise. */
+size_t lgs_table_build_bound(uint32_t n, uint64_t key_bytes, uint64_t value_bytes,
+                             int bits_per_key);
+int lgs_table_build_host(const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
+                         const uint8_t *vals, const uint64_t *val_off, const uint32_t *val_len,
+                         uint32_t n, uint64_t block_size, uint32_t restart_interval,
+                         int compression, int bits_per_key, int internal_keys, uint8_t *file,
+                         size_t file_cap, size_t *file_size);
+
 /* Devices and diagnostics. */
 /* The drop-in's current footprint: pinned and device bytes held by its
    staging slots, the number of slots created (all devices) and the bytes of

@@ -62,6 +62,20 @@ _SIGS = {
                                              C.c_int, _vp, _vp]),
     "lgs_filter_block_match_host": (C.c_int, [_vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_uint32,
                                               C.c_int, _vp]),
+    "lgs_block_build_bound": (C.c_size_t, [C.c_uint32, C.c_uint64, C.c_uint64]),
+    "lgs_block_build_scratch": (C.c_size_t, [C.c_uint32]),
+    "lgs_block_cut_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint32,
+                                    C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "lgs_block_emit_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_int,
+                                     C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
+                                     _vp]),
+    "lgs_block_build_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64,
+                                       C.c_uint32, C.c_int, _vp, C.c_size_t, _vp, _vp, _vp, _vp,
+                                       C.c_size_t, _vp, _vp]),
+    "lgs_table_build_bound": (C.c_size_t, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_int]),
+    "lgs_table_build_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64,
+                                       C.c_uint32, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t,
+                                       C.POINTER(C.c_size_t)]),
     "lgs_dropin_footprint": (C.c_int, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                        C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]),
     "lgs_service_quiesce": (C.c_int, []),

@@ -43,7 +43,9 @@
 
 #include "../../include/lcdb_gpu_snappy.h"
 
+#include "lgs_block.h"
 #include "lgs_launch.h"
+#include "lgs_table_tail.h"
 
 namespace lgs {
 namespace {
@@ -2185,6 +2187,509 @@ int lgs_filter_block_match_host(const uint8_t* block, size_t block_len,
   LGS_HIP(hipMemcpyAsync(h + o_m, d + o_m, nq, hipMemcpyDeviceToHost, c.stream));
   LGS_HIP(hipStreamSynchronize(c.stream));
   memcpy(match, h + o_m, nq);
+  return LGS_OK;
+}
+
+// ---- the data-block builder and whole tables (kernels: lgs_block.hip) ----
+
+namespace {
+
+constexpr uint32_t kMaxEntries = 0x7fffffffu;
+constexpr uint64_t kMaxEntryBytes = 1ull << 30;   // key + value of one entry
+const char kFilterName[] = "filter.leveldb.BuiltinBloomFilter2";   // "filter." + bloom.c's name
+
+// The builder's device scratch (BlockScratch, lgs_launch.h).
+struct BlockBuildScratch {
+  size_t lcp, sh, S, ca, cb, next, ja, jb, mark, bid, icut, ilen, part, total;
+  explicit BlockBuildScratch(uint32_t n) {
+    const size_t m = (size_t)n + 1;
+    Layout L;
+    lcp = L.take(4 * m);
+    sh = L.take(4 * m);
+    S = L.take(8 * m);
+    ca = L.take(8 * m);
+    cb = L.take(8 * m);
+    next = L.take(4 * m);
+    ja = L.take(4 * m);
+    jb = L.take(4 * m);
+    mark = L.take(4 * m);
+    bid = L.take(8 * m);
+    icut = L.take(4 * m);
+    ilen = L.take(4 * m);
+    part = L.take(8 * scan_parts(n) + 8);
+    total = L.at;
+  }
+  BlockScratch at(uint8_t* p) const {
+    return BlockScratch{(uint32_t*)(p + lcp), (uint32_t*)(p + sh), (uint64_t*)(p + S),
+                        (uint64_t*)(p + ca), (uint64_t*)(p + cb), (uint32_t*)(p + next),
+                        (uint32_t*)(p + ja), (uint32_t*)(p + jb), (uint32_t*)(p + mark),
+                        (uint64_t*)(p + bid), (uint32_t*)(p + icut), (uint32_t*)(p + ilen),
+                        (uint64_t*)(p + part)};
+  }
+};
+
+static int block_args(uint32_t n, uint32_t restart_interval, int internal_keys) {
+  if (n > kMaxEntries) return fail(LGS_EINVAL, "%u entries: at most 2^31 - 1", n);
+  if (restart_interval == 0) return fail(LGS_EINVAL, "restart_interval must be at least 1");
+  if (internal_keys != 0 && internal_keys != 1)
+    return fail(LGS_EINVAL, "internal_keys must be 0 or 1");
+  return LGS_OK;
+}
+
+// Host entries staged key after key and value after value (uploads of one
+// _host call), and the checks a _dev caller vouches for.
+struct EntryStage {
+  size_t keys, vals, koff, klen, voff, vlen;
+  uint64_t kb = 0, vb = 0;
+};
+
+static int entries_check(const uint32_t* key_len, const uint32_t* val_len, uint32_t n,
+                         int internal_keys, EntryStage* E) {
+  for (uint32_t i = 0; i < n; ++i) {
+    if ((uint64_t)key_len[i] + val_len[i] >= kMaxEntryBytes)
+      return fail(LGS_EINVAL, "entry %u: key + value of %llu bytes, under 2^30 supported", i,
+                  (unsigned long long)key_len[i] + val_len[i]);
+    if (internal_keys && key_len[i] < 8)
+      return fail(LGS_EINVAL, "entry %u: internal key of %u bytes (at least 8)", i, key_len[i]);
+    E->kb += key_len[i];
+    E->vb += val_len[i];
+  }
+  return LGS_OK;
+}
+
+static void entries_layout(Layout& L, uint32_t n, EntryStage* E) {
+  E->keys = L.take((size_t)E->kb + 16);
+  E->vals = L.take((size_t)E->vb + 16);
+  E->koff = L.take(8 * (size_t)n);
+  E->klen = L.take(4 * (size_t)n);
+  E->voff = L.take(8 * (size_t)n);
+  E->vlen = L.take(4 * (size_t)n);
+}
+
+static void entries_stage(uint8_t* h, const EntryStage& E, const uint8_t* keys,
+                          const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
+                          const uint64_t* val_off, const uint32_t* val_len, uint32_t n) {
+  uint64_t* koff = (uint64_t*)(h + E.koff);
+  uint64_t* voff = (uint64_t*)(h + E.voff);
+  uint64_t ka = 0, va = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    koff[i] = ka;
+    voff[i] = va;
+    ka += key_len[i];
+    va += val_len[i];
+  }
+  memcpy(h + E.klen, key_len, 4 * (size_t)n);
+  memcpy(h + E.vlen, val_len, 4 * (size_t)n);
+  par_for(n, (size_t)(ka + va), [&](uint32_t i0, uint32_t i1) {
+    for (uint32_t i = i0; i < i1; ++i) {
+      memcpy(h + E.keys + koff[i], keys + key_off[i], key_len[i]);
+      memcpy(h + E.vals + voff[i], vals + val_off[i], val_len[i]);
+    }
+  });
+  memset(h + E.keys + ka, 0, 16);
+  memset(h + E.vals + va, 0, 16);
+}
+
+static BlockIn entries_in(uint8_t* d, const EntryStage& E, uint32_t n) {
+  return BlockIn{d + E.keys, (const uint64_t*)(d + E.koff), (const uint32_t*)(d + E.klen),
+                 d + E.vals, (const uint64_t*)(d + E.voff), (const uint32_t*)(d + E.vlen), n};
+}
+
+// The cut's outputs inside an arena.
+struct CutLayout {
+  size_t bf, roff, rlen, ioff;
+  void take(Layout& L, uint32_t n) {
+    bf = L.take(4 * ((size_t)n + 1));
+    roff = L.take(8 * ((size_t)n + 1));
+    rlen = L.take(4 * ((size_t)n + 1));
+    ioff = L.take(8 * ((size_t)n + 1));
+  }
+  BlockCut at(uint8_t* p, uint64_t* counts) const {
+    return BlockCut{(uint32_t*)(p + bf), (uint64_t*)(p + roff), (uint32_t*)(p + rlen),
+                    (uint64_t*)(p + ioff), counts};
+  }
+};
+
+// Index block bound: one block of n entries (restart interval 1) whose keys
+// total key_bytes and whose values are handles of at most 20 bytes.
+static size_t index_block_bound(uint32_t n, uint64_t key_bytes) {
+  return (size_t)(key_bytes + (20ull + 7 + 4) * n + 8);
+}
+
+}  // namespace
+
+size_t lgs_block_build_bound(uint32_t n, uint64_t key_bytes, uint64_t value_bytes) {
+  // Every entry a block of its own: an 11-byte header at most, one restart
+  // and the restart count; 16 readable bytes after the last block.
+  return (size_t)(key_bytes + value_bytes + 19ull * n + 16);
+}
+
+size_t lgs_block_build_scratch(uint32_t n) { return BlockBuildScratch(n).total; }
+
+size_t lgs_table_build_bound(uint32_t n, uint64_t key_bytes, uint64_t value_bytes,
+                             int bits_per_key) {
+  const uint64_t data = key_bytes + value_bytes + 19ull * n + (uint64_t)LGS_TRAILER_SIZE * n;
+  const uint64_t filter =
+      bits_per_key > 0 ? lgs_filter_block_bound(n, n, data, bits_per_key) + LGS_TRAILER_SIZE : 0;
+  return (size_t)(data + filter + kMetaindexMax + LGS_TRAILER_SIZE + index_block_bound(n, key_bytes) +
+                  LGS_TRAILER_SIZE + kFooterSize);
+}
+
+int lgs_block_cut_dev(const uint8_t* d_keys, const uint64_t* d_key_off, const uint32_t* d_key_len,
+                      const uint32_t* d_val_len, uint32_t n, uint64_t block_size,
+                      uint32_t restart_interval, int internal_keys, uint32_t* d_block_first,
+                      uint64_t* d_raw_off, uint32_t* d_raw_len, uint64_t* d_ikey_off,
+                      uint64_t* d_counts, void* d_scratch, size_t scratch_bytes, void* stream) {
+  LGS_TRY(block_args(n, restart_interval, internal_keys));
+  if (!d_block_first || !d_raw_off || !d_raw_len || !d_ikey_off || !d_counts || !d_scratch ||
+      (n && (!d_keys || !d_key_off || !d_key_len || !d_val_len)))
+    return fail(LGS_EINVAL, "NULL argument");
+  const BlockBuildScratch B(n);
+  if (scratch_bytes < B.total)
+    return fail(LGS_EINVAL, "scratch %zu < %zu (lgs_block_build_scratch)", scratch_bytes, B.total);
+  const BlockIn in{d_keys, d_key_off, d_key_len, nullptr, nullptr, d_val_len, n};
+  const BlockCut out{d_block_first, d_raw_off, d_raw_len, d_ikey_off, d_counts};
+  LGS_HIP(launch_block_cut(in, block_size, restart_interval, internal_keys ? 8u : 0u,
+                           B.at((uint8_t*)d_scratch), out, (hipStream_t)stream));
+  return LGS_OK;
+}
+
+int lgs_block_emit_dev(const uint8_t* d_keys, const uint64_t* d_key_off, const uint32_t* d_key_len,
+                       const uint8_t* d_vals, const uint64_t* d_val_off, const uint32_t* d_val_len,
+                       uint32_t n, uint32_t restart_interval, int internal_keys, uint32_t nblocks,
+                       const uint32_t* d_block_first, const uint64_t* d_raw_off,
+                       const uint32_t* d_raw_len, uint8_t* d_raw, const uint64_t* d_ikey_off,
+                       uint8_t* d_ikey, void* d_scratch, size_t scratch_bytes, void* stream) {
+  LGS_TRY(block_args(n, restart_interval, internal_keys));
+  if (nblocks > n) return fail(LGS_EINVAL, "%u blocks of %u entries", nblocks, n);
+  if (n == 0) return LGS_OK;
+  if (!d_keys || !d_key_off || !d_key_len || !d_vals || !d_val_off || !d_val_len ||
+      !d_block_first || !d_raw_off || !d_raw_len || !d_raw || !d_scratch || (d_ikey && !d_ikey_off))
+    return fail(LGS_EINVAL, "NULL argument");
+  const BlockBuildScratch B(n);
+  if (scratch_bytes < B.total)
+    return fail(LGS_EINVAL, "scratch %zu < %zu (lgs_block_build_scratch)", scratch_bytes, B.total);
+  const BlockIn in{d_keys, d_key_off, d_key_len, d_vals, d_val_off, d_val_len, n};
+  LGS_HIP(launch_block_emit(in, restart_interval, internal_keys ? 8u : 0u, nblocks,
+                            B.at((uint8_t*)d_scratch), d_block_first, d_raw_off, d_raw_len, d_raw,
+                            d_ikey_off, d_ikey, (hipStream_t)stream));
+  return LGS_OK;
+}
+
+int lgs_block_build_host(const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
+                         const uint8_t* vals, const uint64_t* val_off, const uint32_t* val_len,
+                         uint32_t n, uint64_t block_size, uint32_t restart_interval,
+                         int internal_keys, uint8_t* raw, size_t raw_cap, uint64_t* raw_off,
+                         uint32_t* raw_len, uint32_t* block_first, uint8_t* ikey, size_t ikey_cap,
+                         uint64_t* ikey_off, uint32_t* nblocks) {
+  LGS_TRY(block_args(n, restart_interval, internal_keys));
+  if (!raw_off || !raw_len || !block_first || !ikey_off || !nblocks ||
+      (n && (!keys || !key_off || !key_len || !vals || !val_off || !val_len || !raw || !ikey)))
+    return fail(LGS_EINVAL, "NULL argument");
+  EntryStage E;
+  LGS_TRY(entries_check(key_len, val_len, n, internal_keys, &E));
+  *nblocks = 0;
+  block_first[0] = 0;
+  raw_off[0] = 0;
+  ikey_off[0] = 0;
+  if (n == 0) return LGS_OK;
+  Lease lease(batch_pool());
+  LGS_TRY(lease.acquire());
+  Ctx& c = lease.ctx();
+  const size_t bound = lgs_block_build_bound(n, E.kb, E.vb);
+  const BlockBuildScratch B(n);
+  Layout L;  // uploads | downloads | device-only
+  entries_layout(L, n, &E);
+  const size_t up_end = L.at;
+  const size_t o_cnt = L.take(8 * kBlockCounts);
+  CutLayout K;
+  K.take(L, n);
+  const size_t o_raw = L.take(bound);
+  const size_t o_ikey = L.take((size_t)E.kb + 16);
+  const size_t pin_end = L.at;
+  const size_t o_scr = L.take(B.total);
+  LGS_TRY(ctx_reserve(c, L.at, pin_end));
+  uint8_t* h = c.h_buf;
+  uint8_t* d = c.d_buf;
+  entries_stage(h, E, keys, key_off, key_len, vals, val_off, val_len, n);
+  LGS_HIP(hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, c.stream));
+  const BlockIn in = entries_in(d, E, n);
+  const BlockCut cut = K.at(d, (uint64_t*)(d + o_cnt));
+  const uint32_t trim = internal_keys ? 8u : 0u;
+  LGS_HIP(launch_block_cut(in, block_size, restart_interval, trim, B.at(d + o_scr), cut, c.stream));
+  LGS_HIP(hipMemcpyAsync(h + o_cnt, d + o_cnt, 8 * kBlockCounts, hipMemcpyDeviceToHost, c.stream));
+  LGS_HIP(hipStreamSynchronize(c.stream));
+  const uint64_t* cnt = (const uint64_t*)(h + o_cnt);
+  const uint64_t nb = cnt[0], raw_total = cnt[1], ikey_total = cnt[3];
+  if (nb > n || raw_total + 16 > bound || ikey_total > E.kb)
+    return fail(LGS_EINTERNAL, "cut of %u entries: %llu blocks, %llu + %llu bytes", n,
+                (unsigned long long)nb, (unsigned long long)raw_total,
+                (unsigned long long)ikey_total);
+  if (cnt[2] > 0x7fffffffull)
+    return fail(LGS_EINVAL, "a block of %llu bytes: under 2^31 supported",
+                (unsigned long long)cnt[2]);
+  if (raw_total > raw_cap || ikey_total > ikey_cap)
+    return fail(LGS_ENOSPC, "blocks need %llu bytes (raw_cap %zu), index keys %llu (ikey_cap %zu)",
+                (unsigned long long)raw_total, raw_cap, (unsigned long long)ikey_total, ikey_cap);
+  LGS_HIP(launch_block_emit(in, restart_interval, trim, (uint32_t)nb, B.at(d + o_scr),
+                            cut.block_first, cut.raw_off, cut.raw_len, d + o_raw, cut.ikey_off,
+                            d + o_ikey, c.stream));
+  LGS_HIP(hipMemcpyAsync(h + K.bf, d + K.bf, o_raw - K.bf, hipMemcpyDeviceToHost, c.stream));
+  LGS_HIP(hipMemcpyAsync(h + o_raw, d + o_raw, (size_t)raw_total, hipMemcpyDeviceToHost, c.stream));
+  LGS_HIP(hipMemcpyAsync(h + o_ikey, d + o_ikey, (size_t)ikey_total, hipMemcpyDeviceToHost,
+                         c.stream));
+  LGS_HIP(hipStreamSynchronize(c.stream));
+  memcpy(block_first, h + K.bf, 4 * ((size_t)nb + 1));
+  memcpy(raw_off, h + K.roff, 8 * ((size_t)nb + 1));
+  memcpy(raw_len, h + K.rlen, 4 * (size_t)nb);
+  memcpy(ikey_off, h + K.ioff, 8 * ((size_t)nb + 1));
+  memcpy(raw, h + o_raw, (size_t)raw_total);
+  memcpy(ikey, h + o_ikey, (size_t)ikey_total);
+  *nblocks = (uint32_t)nb;
+  return LGS_OK;
+}
+
+int lgs_table_build_host(const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
+                         const uint8_t* vals, const uint64_t* val_off, const uint32_t* val_len,
+                         uint32_t n, uint64_t block_size, uint32_t restart_interval,
+                         int compression, int bits_per_key, int internal_keys, uint8_t* file,
+                         size_t file_cap, size_t* file_size) {
+  LGS_TRY(block_args(n, restart_interval, internal_keys));
+  if (compression != LGS_NO_COMPRESSION && compression != LGS_SNAPPY_COMPRESSION)
+    return fail(LGS_EINVAL, "unknown compression type %d", compression);
+  if (bits_per_key < 0 || bits_per_key > kMaxBitsPerKey)
+    return fail(LGS_EINVAL, "bits_per_key %d out of range", bits_per_key);
+  if (!file || !file_size || (n && (!keys || !key_off || !key_len || !vals || !val_off || !val_len)))
+    return fail(LGS_EINVAL, "NULL argument");
+  EntryStage E;
+  LGS_TRY(entries_check(key_len, val_len, n, internal_keys, &E));
+  // The smallest table: two 8-byte blocks with trailers and the footer.
+  if (file_cap < 2 * (8 + LGS_TRAILER_SIZE) + kFooterSize)
+    return fail(LGS_ENOSPC, "file_cap %zu: no table fits", file_cap);
+  Lease lease(batch_pool());
+  LGS_TRY(lease.acquire());
+  Ctx& c = lease.ctx();
+  const uint32_t trim = internal_keys ? 8u : 0u;
+  const bool filter = bits_per_key > 0;
+  const size_t raw_bound = lgs_block_build_bound(n, E.kb, E.vb);
+  const uint64_t data_bound = raw_bound + (uint64_t)LGS_TRAILER_SIZE * n;
+  if (data_bound >= kMaxDataEnd) return fail(LGS_EINVAL, "table of %llu bytes too large",
+                                             (unsigned long long)data_bound);
+  const size_t fbound = filter ? lgs_filter_block_bound(n, n, data_bound, bits_per_key) : 0;
+  const size_t ibound = index_block_bound(n, E.kb);
+  if (fbound > 0x7fffffffull || ibound > 0x7fffffffull)
+    return fail(LGS_EINVAL, "filter or index block over 2^31 bytes");
+  const size_t img_bound = lgs_table_build_bound(n, E.kb, E.vb, bits_per_key);
+  const BlockBuildScratch B(n);
+  const FilterScratch F(data_bound);
+  size_t wtotal = WriteScratch(n, raw_bound).total;
+  if (WriteScratch(1, fbound).total > wtotal) wtotal = WriteScratch(1, fbound).total;
+  Layout L;  // uploads | small downloads | device-only
+  entries_layout(L, n, &E);
+  const size_t up_end = L.at;
+  const size_t o_meta = L.take(kMetaindexMax + 16);   // tail uploads: metaindex, {offset, length} x 2
+  const size_t o_toff = L.take(16);
+  const size_t o_tlen = L.take(8);
+  const size_t o_tencoff = L.take(16);
+  // The tail's encoder items: the metaindex block and the index block's 64 KiB
+  // chunks ({input offset, output slot} u64, {length, header} u32 each).
+  const uint32_t icap = 2 + (uint32_t)(ibound / kChunk);
+  const size_t o_titems = L.take(24 * (size_t)icap);
+  const size_t o_cnt = L.take(8 * kBlockCounts);      // downloads
+  const size_t o_cnt2 = L.take(8 * kBlockCounts);
+  const size_t o_end = L.take(8);
+  const size_t o_fsize = L.take(8);
+  const size_t o_thoff = L.take(16);
+  const size_t o_thsize = L.take(16);
+  const size_t pin_end = L.at;
+  CutLayout K, K2;
+  K.take(L, n);
+  K2.take(L, n);
+  const size_t o_raw = L.take(raw_bound);
+  const size_t o_ikey = L.take((size_t)E.kb + 16);
+  const size_t o_scr = L.take(B.total);
+  const size_t o_wscr = L.take(wtotal);
+  const size_t o_hoff = L.take(8 * (size_t)n + 8);
+  const size_t o_hsize = L.take(8 * (size_t)n + 8);
+  const size_t o_fscr = L.take(F.total);
+  const size_t o_fout = L.take(fbound + 16);
+  const size_t o_hval = L.take(20 * (size_t)n + 16);
+  const size_t o_ivoff = L.take(8 * (size_t)n + 8);
+  const size_t o_ivlen = L.take(4 * (size_t)n + 4);
+  const size_t o_iklen = L.take(4 * (size_t)n + 4);
+  const size_t o_iraw = L.take(ibound + 16);
+  const size_t o_file = L.take(img_bound + 16);
+  const size_t o_tslots = L.take((size_t)icap * chunk_out(kChunk));
+  const size_t o_tpacked = L.take(bound_of(ibound) + 64);
+  const size_t o_tenclen = L.take(4 * (size_t)icap);
+  const size_t o_tenclen2 = L.take(8);
+  const size_t o_tpoff = L.take(8 * (size_t)icap);
+  const size_t o_tptotal = L.take(8);
+  const size_t o_tfoff = L.take(16);
+  const size_t o_tpart = L.take(8 * scan_parts(icap) + 16);
+  LGS_TRY(ctx_reserve(c, L.at, pin_end));
+  uint8_t* h = c.h_buf;
+  uint8_t* d = c.d_buf;
+  hipStream_t s = c.stream;
+  uint64_t nb = 0, raw_total = 0, max_raw = 0;
+  const BlockIn in = entries_in(d, E, n);
+  const BlockCut cut = K.at(d, (uint64_t*)(d + o_cnt));
+  if (n) {
+    entries_stage(h, E, keys, key_off, key_len, vals, val_off, val_len, n);
+    LGS_HIP(hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, s));
+    LGS_HIP(launch_block_cut(in, block_size, restart_interval, trim, B.at(d + o_scr), cut, s));
+    LGS_HIP(hipMemcpyAsync(h + o_cnt, d + o_cnt, 8 * kBlockCounts, hipMemcpyDeviceToHost, s));
+    LGS_HIP(hipStreamSynchronize(s));
+    const uint64_t* cnt = (const uint64_t*)(h + o_cnt);
+    nb = cnt[0], raw_total = cnt[1], max_raw = cnt[2];
+    if (nb == 0 || nb > n || raw_total + 16 > raw_bound || cnt[3] > E.kb)
+      return fail(LGS_EINTERNAL, "cut of %u entries: %llu blocks, %llu bytes", n,
+                  (unsigned long long)nb, (unsigned long long)raw_total);
+    if (max_raw > 0x7fffffffull)
+      return fail(LGS_EINVAL, "a block of %llu bytes: under 2^31 supported",
+                  (unsigned long long)max_raw);
+  } else {
+    LGS_HIP(hipMemsetAsync(d + K.bf, 0, 4, s));
+  }
+  // Data blocks (table_builder.c:215-278), framed from file offset 0.
+  uint64_t* d_hoff = (uint64_t*)(d + o_hoff);
+  uint64_t* d_hsize = (uint64_t*)(d + o_hsize);
+  uint64_t data_end = 0;
+  const BlockCut cut2 = K2.at(d, (uint64_t*)(d + o_cnt2));
+  const BlockIn iin{d + o_ikey, cut.ikey_off, (const uint32_t*)(d + o_iklen), d + o_hval,
+                    (const uint64_t*)(d + o_ivoff), (const uint32_t*)(d + o_ivlen), (uint32_t)nb};
+  uint64_t index_len = 0;
+  if (nb) {
+    LGS_HIP(launch_block_emit(in, restart_interval, trim, (uint32_t)nb, B.at(d + o_scr),
+                              cut.block_first, cut.raw_off, cut.raw_len, d + o_raw, cut.ikey_off,
+                              d + o_ikey, s));
+    LGS_TRY(table_write(d + o_raw, cut.raw_off, cut.raw_len, (uint32_t)nb, (uint32_t)max_raw,
+                        compression, 0, d + o_file, d_hoff, d_hsize, (uint64_t*)(d + o_end),
+                        d + o_wscr, WriteScratch((uint32_t)nb, raw_total), s));
+    // The index block's entries (:229-239, :332-341): index key -> handle, one
+    // block whatever its size, restart interval 1 (:87).
+    LGS_HIP(launch_handle_values(d_hoff, d_hsize, cut.ikey_off, (uint32_t)nb, d + o_hval,
+                                 (uint64_t*)(d + o_ivoff), (uint32_t*)(d + o_ivlen),
+                                 (uint32_t*)(d + o_iklen), s));
+    LGS_HIP(launch_block_cut(iin, ~0ull, 1, 0, B.at(d + o_scr), cut2, s));
+    LGS_HIP(hipMemcpyAsync(h + o_cnt2, d + o_cnt2, 8 * kBlockCounts, hipMemcpyDeviceToHost, s));
+    LGS_HIP(hipMemcpyAsync(h + o_end, d + o_end, 8, hipMemcpyDeviceToHost, s));
+    LGS_HIP(hipStreamSynchronize(s));
+    data_end = *(const uint64_t*)(h + o_end);
+    const uint64_t* cnt2 = (const uint64_t*)(h + o_cnt2);
+    index_len = cnt2[1];
+    if (data_end > data_bound || cnt2[0] != 1 || index_len > ibound)
+      return fail(LGS_EINTERNAL, "data blocks end at %llu, index block of %llu bytes",
+                  (unsigned long long)data_end, (unsigned long long)index_len);
+    LGS_HIP(launch_block_emit(iin, 1, 0, 1, B.at(d + o_scr), cut2.block_first, cut2.raw_off,
+                              cut2.raw_len, d + o_iraw, nullptr, nullptr, s));
+  } else {
+    // An index block with no entries (block_builder.c:68, :143-146).
+    index_len = tail_metaindex(h + o_meta, kMetaindexMax, nullptr, 0, 0);
+    LGS_HIP(hipMemcpyAsync(d + o_iraw, h + o_meta, (size_t)index_len, hipMemcpyHostToDevice, s));
+    LGS_HIP(hipStreamSynchronize(s));
+  }
+  // The filter block (:292-299), stored raw after the data blocks.
+  uint64_t at = data_end, filter_size = 0;
+  if (filter) {
+    LGS_TRY(lgs_filter_block_build_dev(in.keys, in.key_off, in.key_len, n, cut.block_first, d_hoff,
+                                       (uint32_t)nb, data_end, bits_per_key, internal_keys,
+                                       d + o_fout, fbound, (uint64_t*)(d + o_fsize), d + o_fscr,
+                                       F.total, s));
+    LGS_HIP(hipMemcpyAsync(h + o_fsize, d + o_fsize, 8, hipMemcpyDeviceToHost, s));
+    LGS_HIP(hipStreamSynchronize(s));
+    filter_size = *(const uint64_t*)(h + o_fsize);
+    if (filter_size > fbound)
+      return fail(LGS_EINTERNAL, "filter block %llu > bound %zu", (unsigned long long)filter_size,
+                  fbound);
+    *(uint64_t*)(h + o_toff) = 0;
+    *(uint32_t*)(h + o_tlen) = (uint32_t)filter_size;
+    LGS_HIP(hipMemcpyAsync(d + o_toff, h + o_toff, 8, hipMemcpyHostToDevice, s));
+    LGS_HIP(hipMemcpyAsync(d + o_tlen, h + o_tlen, 4, hipMemcpyHostToDevice, s));
+    LGS_TRY(table_write(d + o_fout, (const uint64_t*)(d + o_toff), (const uint32_t*)(d + o_tlen), 1,
+                        (uint32_t)filter_size, LGS_NO_COMPRESSION, at, d + o_file + at,
+                        (uint64_t*)(d + o_thoff), (uint64_t*)(d + o_thsize), nullptr, d + o_wscr,
+                        WriteScratch(1, filter_size), s));
+    // The pinned words are reused below: the uploads must have left them.
+    LGS_HIP(hipStreamSynchronize(s));
+    at += filter_size + LGS_TRAILER_SIZE;
+  }
+  // Metaindex (:301-328) and index (:330-344) blocks, both through the
+  // table's compression like every block ldb_tablegen_write_block writes.
+  // The index block grows with the table (C5: 36 MB), and one block is one
+  // wave's work in the encoder, 64 KiB chunk after chunk; the chunks are
+  // independent (snappy.c:370-381), so they are encoded here as items of
+  // their own, as ldb_snappy_encode does, and packed into the block's stream.
+  const size_t meta_len = tail_metaindex(h + o_meta, kMetaindexMax, filter ? kFilterName : nullptr,
+                                         data_end, filter_size);
+  if (meta_len == 0) return fail(LGS_EINTERNAL, "metaindex block does not fit");
+  const bool snappy = compression == LGS_SNAPPY_COMPRESSION;
+  uint64_t* toff = (uint64_t*)(h + o_toff);
+  uint32_t* tlen = (uint32_t*)(h + o_tlen);
+  uint64_t* tenc_off = (uint64_t*)(h + o_tencoff);
+  toff[0] = o_meta;          // offsets from the arena's start
+  toff[1] = o_iraw;
+  tlen[0] = (uint32_t)meta_len;
+  tlen[1] = (uint32_t)index_len;
+  tenc_off[0] = o_tslots;
+  tenc_off[1] = o_tpacked;
+  const uint32_t items = 1 + (uint32_t)((index_len + kChunk - 1) / kChunk);
+  if (items > icap) return fail(LGS_EINTERNAL, "index block of %llu bytes",
+                                (unsigned long long)index_len);
+  uint64_t* it_in = (uint64_t*)(h + o_titems);
+  uint64_t* it_out = it_in + icap;
+  uint32_t* it_len = (uint32_t*)(it_out + icap);
+  uint32_t* it_hdr = it_len + icap;
+  it_in[0] = o_meta;
+  it_len[0] = it_hdr[0] = (uint32_t)meta_len;
+  it_out[0] = o_tslots;
+  size_t slot = o_tslots + chunk_out((uint32_t)meta_len);
+  for (uint32_t j = 1; j < items; ++j) {
+    const uint64_t off = (uint64_t)(j - 1) * kChunk;
+    it_in[j] = o_iraw + off;
+    it_len[j] = (uint32_t)(index_len - off < kChunk ? index_len - off : kChunk);
+    it_hdr[j] = j == 1 ? (uint32_t)index_len : 0xffffffffu;      // snappy.c:368
+    it_out[j] = slot;
+    slot += chunk_out(it_len[j]);
+  }
+  LGS_HIP(hipMemcpyAsync(d + o_meta, h + o_meta, o_cnt - o_meta, hipMemcpyHostToDevice, s));
+  uint64_t* part = (uint64_t*)(d + o_tpart);
+  uint32_t* enc_len = (uint32_t*)(d + o_tenclen);
+  uint32_t* enc_len2 = (uint32_t*)(d + o_tenclen2);
+  if (snappy) {
+    const uint64_t* d_out = (const uint64_t*)(d + o_titems) + icap;
+    const uint32_t* d_len = (const uint32_t*)(d_out + icap);
+    EncodeArgs ea{d, (const uint64_t*)(d + o_titems), d_len, d, d_out, enc_len, d_len + icap,
+                  nullptr, items, nullptr};
+    const uint32_t ichunk = (uint32_t)(index_len < kChunk ? index_len : kChunk);
+    LGS_HIP(launch_encode(ea, meta_len > ichunk ? (uint32_t)meta_len : ichunk, s));
+    LGS_HIP(launch_scan(2, nullptr, enc_len + 1, part, 0, (uint64_t*)(d + o_tpoff),
+                        (uint64_t*)(d + o_tptotal), items - 1, s));
+    LGS_HIP(launch_pack(d, d_out + 1, enc_len + 1, d + o_tpacked, (const uint64_t*)(d + o_tpoff),
+                        items - 1, s));
+    LGS_HIP(launch_pair_lens(enc_len, (const uint64_t*)(d + o_tptotal), enc_len2, s));
+  }
+  LGS_HIP(launch_scan(1, (const uint32_t*)(d + o_tlen), snappy ? enc_len2 : nullptr, part, at,
+                      (uint64_t*)(d + o_tfoff), (uint64_t*)(d + o_end), 2, s));
+  const FrameArgs fa{d, (const uint64_t*)(d + o_toff), (const uint32_t*)(d + o_tlen), d,
+                     (const uint64_t*)(d + o_tencoff), snappy ? enc_len2 : nullptr,
+                     d + o_file + at, at, (const uint64_t*)(d + o_tfoff),
+                     (uint64_t*)(d + o_thoff), (uint64_t*)(d + o_thsize), 2};
+  LGS_HIP(launch_frame(fa, s));
+  LGS_HIP(hipMemcpyAsync(h + o_end, d + o_end, pin_end - o_end, hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipStreamSynchronize(s));
+  const uint64_t end = *(const uint64_t*)(h + o_end);
+  const uint64_t* thoff = (const uint64_t*)(h + o_thoff);
+  const uint64_t* thsize = (const uint64_t*)(h + o_thsize);
+  if (end > img_bound)
+    return fail(LGS_EINTERNAL, "table of %llu bytes > bound %zu", (unsigned long long)end, img_bound);
+  *file_size = (size_t)(end + kFooterSize);
+  if (end + kFooterSize > file_cap)
+    return fail(LGS_ENOSPC, "table needs %llu bytes, file_cap %zu",
+                (unsigned long long)(end + kFooterSize), file_cap);
+  LGS_HIP(hipMemcpyAsync(file, d + o_file, (size_t)end, hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipStreamSynchronize(s));
+  tail_footer(file + end, thoff[0], thsize[0], thoff[1], thsize[1]);   // :346-362
   return LGS_OK;
 }
 

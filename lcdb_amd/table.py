@@ -12,6 +12,9 @@ the batched C ABI that does both for many blocks per launch
 * ``read_blocks``     -- ``ldb_read_block`` for n handles
   (src/table/format.c:162-270): truncation, checksum, type, raw or decode;
 * ``*_host`` variants on host bytes (pinned staging inside the library);
+* ``build_blocks``    -- ``ldb_tablegen_add``'s data blocks and index keys from
+  sorted entries (src/table/table_builder.c:215-255, block_builder.c:91-158);
+* ``build_table_host`` -- the whole ``.ldb`` of ``ldb_tablegen_*`` (:215-365);
 * ``index_host``      -- ``ldb_table_open``'s footer, index-block handles and
   metaindex filter handle (src/table/table.c:78-180), the handles the batched
   read takes.
@@ -34,7 +37,7 @@ _L = _native.lib()
 
 __all__ = [
     "crc32c_batch", "write_blocks", "read_blocks", "write_blocks_host", "read_blocks_host",
-    "index_host", "FILTER_NAME",
+    "index_host", "FILTER_NAME", "build_blocks", "build_blocks_host", "build_table_host",
     "LGS_NO_COMPRESSION", "LGS_SNAPPY_COMPRESSION", "LGS_TRAILER_SIZE", "LGS_ST_OK",
     "LGS_ST_CORRUPT", "LGS_ST_NOSPACE", "LGS_ST_IOERR", "LGS_ST_BADCRC", "LGS_ST_BADTYPE",
 ]
@@ -128,9 +131,118 @@ def read_blocks(d_file, file_len: int, d_hoff, d_hsize, d_out, d_out_off, d_out_
     return d_out_len, d_status
 
 
+def build_blocks(d_keys, d_key_off, d_key_len, d_vals, d_val_off, d_val_len,
+                 block_size: int = 4096, restart_interval: int = 16,
+                 internal_keys: bool = False, stream=None):
+    """lcdb's data blocks of n sorted entries (lgs_block_cut_dev + one
+    read-back of the counts + lgs_block_emit_dev).
+
+    Returns a dict of device tensors: ``raw`` (the packed blocks, 16 spare
+    bytes), ``raw_off`` / ``raw_len`` (write_blocks' input), ``block_first``
+    (nblocks + 1), ``ikey`` / ``ikey_off`` (nblocks + 1), and the ints
+    ``nblocks``, ``raw_total``, ``max_len``.  Inputs must stay readable 16
+    bytes past their end."""
+    torch = _torch()
+    n = int(d_key_len.numel())
+    dev = d_keys.device
+    sp = _stream_ptr(stream)
+    scr = torch.empty(max(int(_L.lgs_block_build_scratch(n)), 1), dtype=torch.uint8, device=dev)
+    first = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    raw_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    raw_len = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    ikey_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    counts = torch.zeros(4, dtype=torch.int64, device=dev)
+    check(_L.lgs_block_cut_dev(d_keys.data_ptr(), d_key_off.data_ptr(), d_key_len.data_ptr(),
+                               d_val_len.data_ptr(), n, int(block_size), int(restart_interval),
+                               1 if internal_keys else 0, first.data_ptr(), raw_off.data_ptr(),
+                               raw_len.data_ptr(), ikey_off.data_ptr(), counts.data_ptr(),
+                               scr.data_ptr(), int(scr.numel()), sp), "lgs_block_cut_dev")
+    if stream is not None:
+        stream.synchronize()
+    nb, raw_total, max_len, ikey_total = (int(x) for x in counts.cpu())
+    raw = torch.empty(raw_total + 16, dtype=torch.uint8, device=dev)
+    ikey = torch.empty(ikey_total + 16, dtype=torch.uint8, device=dev)
+    check(_L.lgs_block_emit_dev(d_keys.data_ptr(), d_key_off.data_ptr(), d_key_len.data_ptr(),
+                                d_vals.data_ptr(), d_val_off.data_ptr(), d_val_len.data_ptr(), n,
+                                int(restart_interval), 1 if internal_keys else 0, nb,
+                                first.data_ptr(), raw_off.data_ptr(), raw_len.data_ptr(),
+                                raw.data_ptr(), ikey_off.data_ptr(), ikey.data_ptr(),
+                                scr.data_ptr(), int(scr.numel()), sp), "lgs_block_emit_dev")
+    if stream is not None:
+        scr.record_stream(stream)
+    return {"raw": raw, "raw_off": raw_off[:nb + 1], "raw_len": raw_len[:nb],
+            "block_first": first[:nb + 1], "ikey": ikey, "ikey_off": ikey_off[:nb + 1],
+            "nblocks": nb, "raw_total": raw_total, "max_len": max_len}
+
+
 # ---------------------------------------------------------------------------
 # Host bytes.
 # ---------------------------------------------------------------------------
+
+def _pack_entries(entries):
+    """(keys, key_off, key_len, vals, val_off, val_len) numpy arrays."""
+    n = len(entries)
+    klen = np.array([len(k) for k, _ in entries], dtype=np.uint32)
+    vlen = np.array([len(v) for _, v in entries], dtype=np.uint32)
+    koff = np.zeros(n, dtype=np.uint64)
+    voff = np.zeros(n, dtype=np.uint64)
+    if n:
+        koff[1:] = np.cumsum(klen[:-1], dtype=np.uint64)
+        voff[1:] = np.cumsum(vlen[:-1], dtype=np.uint64)
+    keys = np.frombuffer(b"".join(k for k, _ in entries) + b"\0" * 16, dtype=np.uint8)
+    vals = np.frombuffer(b"".join(v for _, v in entries) + b"\0" * 16, dtype=np.uint8)
+    return keys, koff, klen, vals, voff, vlen
+
+
+def build_blocks_host(entries, block_size: int = 4096, restart_interval: int = 16,
+                      internal_keys: bool = False):
+    """Returns (data blocks, block_first, index keys) of sorted (key, value)
+    entries: what ldb_tablegen_add cuts and adds to its index block."""
+    import ctypes as C
+    n = len(entries)
+    keys, koff, klen, vals, voff, vlen = _pack_entries(entries)
+    kb, vb = int(klen.sum()), int(vlen.sum())
+    cap = int(_L.lgs_block_build_bound(n, kb, vb))
+    raw = np.empty(cap, dtype=np.uint8)
+    raw_off = np.zeros(n + 1, dtype=np.uint64)
+    raw_len = np.zeros(max(n, 1), dtype=np.uint32)
+    first = np.zeros(n + 1, dtype=np.uint32)
+    ikey = np.empty(kb + 16, dtype=np.uint8)
+    ikey_off = np.zeros(n + 1, dtype=np.uint64)
+    nb = C.c_uint32(0)
+    check(_L.lgs_block_build_host(keys.ctypes.data, koff.ctypes.data, klen.ctypes.data,
+                                  vals.ctypes.data, voff.ctypes.data, vlen.ctypes.data, n,
+                                  int(block_size), int(restart_interval),
+                                  1 if internal_keys else 0, raw.ctypes.data, cap,
+                                  raw_off.ctypes.data, raw_len.ctypes.data, first.ctypes.data,
+                                  ikey.ctypes.data, kb + 16, ikey_off.ctypes.data, C.byref(nb)),
+          "lgs_block_build_host")
+    m = nb.value
+    blocks = [raw[int(raw_off[b]):int(raw_off[b]) + int(raw_len[b])].tobytes() for b in range(m)]
+    ikeys = [ikey[int(ikey_off[b]):int(ikey_off[b + 1])].tobytes() for b in range(m)]
+    return blocks, [int(x) for x in first[:m + 1]], ikeys
+
+
+def build_table_host(entries, block_size: int = 4096, restart_interval: int = 16,
+                     compression: int = LGS_SNAPPY_COMPRESSION, bits_per_key: int = 0,
+                     internal_keys: bool = False, file_cap: Optional[int] = None) -> bytes:
+    """The .ldb lcdb's table builder writes for sorted (key, value) entries
+    (lgs_table_build_host)."""
+    import ctypes as C
+    n = len(entries)
+    keys, koff, klen, vals, voff, vlen = _pack_entries(entries)
+    if file_cap is None:
+        file_cap = int(_L.lgs_table_build_bound(n, int(klen.sum()), int(vlen.sum()),
+                                                int(bits_per_key)))
+    file = np.empty(max(int(file_cap), 1), dtype=np.uint8)
+    size = C.c_size_t(0)
+    check(_L.lgs_table_build_host(keys.ctypes.data, koff.ctypes.data, klen.ctypes.data,
+                                  vals.ctypes.data, voff.ctypes.data, vlen.ctypes.data, n,
+                                  int(block_size), int(restart_interval), int(compression),
+                                  int(bits_per_key), 1 if internal_keys else 0,
+                                  file.ctypes.data, int(file_cap), C.byref(size)),
+          "lgs_table_build_host")
+    return file[:size.value].tobytes()
 
 def write_blocks_host(blocks: Sequence[bytes], compression: int = LGS_SNAPPY_COMPRESSION,
                       base: int = 0):
