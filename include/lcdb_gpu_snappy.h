@@ -390,6 +390,71 @@ int lgs_table_build_host(const uint8_t *keys, const uint64_t *key_off, const uin
                          int compression, int bits_per_key, int internal_keys, uint8_t *file,
                          size_t file_cap, size_t *file_size);
 
+/* ---- batched point lookups ----
+ *
+ * ldb_blockiter_create + one ldb_blockiter_seek on the fresh iterator
+ * (block.c:324-451) for nq independent queries.  Query q seeks key
+ * d_keys[d_key_off[q] .. + d_key_len[q]) in block d_query_block[q]; block b =
+ * d_blocks[d_block_off[b] .. + d_block_len[b]), a decoded block as
+ * lgs_table_read_dev leaves it.  A query block index >= nblocks (0xffffffff
+ * by convention) names no block: no entry, LGS_ST_OK.  d_block_status may be
+ * NULL, else a block whose status != LGS_ST_OK yields that status and no
+ * entry (an error iterator, table.c:286-297).  internal_keys = 0: lcdb's
+ * bytewise comparator; 1: ldb_ikc_compare (dbformat.c:206-230), and a target
+ * or stored key under 8 bytes is corrupt as block.c has it.  No other
+ * comparator is supported.  The outcome is the reference's for any block
+ * contents, sorted or not; nothing outside a block's bytes and a key's bytes
+ * is read.
+ *
+ * Outputs per query: d_entry_pos (offset of the found entry in its block,
+ * 0xffffffff = no entry), d_found_key_len, d_val_pos / d_val_len (the value,
+ * an offset into the block), d_status (LGS_ST_OK, LGS_ST_CORRUPT or the
+ * block's status); if d_key_out != NULL the found entry's full key, its first
+ * min(length, d_key_out_cap[q]) bytes at d_key_out + d_key_out_off[q].
+ * d_scratch: lgs_block_seek_scratch(nq) device bytes.  Asynchronous. */
+size_t lgs_block_seek_scratch(uint32_t nq);
+int lgs_block_seek_dev(const uint8_t *d_blocks, const uint64_t *d_block_off,
+                       const uint32_t *d_block_len, const uint8_t *d_block_status,
+                       uint32_t nblocks, const uint32_t *d_query_block, const uint8_t *d_keys,
+                       const uint64_t *d_key_off, const uint32_t *d_key_len, uint32_t nq,
+                       int internal_keys, uint32_t *d_entry_pos, uint32_t *d_found_key_len,
+                       uint32_t *d_val_pos, uint32_t *d_val_len, uint8_t *d_status,
+                       uint8_t *d_key_out, const uint64_t *d_key_out_off,
+                       const uint32_t *d_key_out_cap, void *d_scratch, size_t scratch_bytes,
+                       void *stream);
+
+/* What version_set.c's save_value (:373-388) leaves in its saver. */
+#define LGS_GET_NOTFOUND  0
+#define LGS_GET_FOUND     1
+#define LGS_GET_DELETED   2
+#define LGS_GET_CORRUPT   3
+
+/* ldb_table_internal_get (table.c:314-364) for nq keys against one table
+   image (file[0 .. file_len), e.g. an mmap'd .ldb), opened as ldb_table_open
+   opens it (paranoid_checks: the index and filter blocks' checksums;
+   filter_name as for lgs_table_index_host, NULL = no filter policy).  Key q =
+   keys[key_off[q] .. + key_len[q]).  Per query: called[q] = 1 when
+   handle_result would be called, then its key and value are
+   out[out_key_off[q] .. out_val_off[q]) and out[out_val_off[q] ..
+   out_key_off[q + 1]) (nq + 1 offsets each, results packed in query order);
+   status[q] = the LGS_ST_* of the rc the reference returns (LGS_ST_OK,
+   LGS_ST_CORRUPT, or a block read's LGS_ST_IOERR / _BADCRC / _BADTYPE).  A
+   table that does not open (short file, bad footer, unreadable index block)
+   gives every query that status and no result.  verdict (may be NULL; with
+   internal_keys = 1): LGS_GET_* for the found entry against key q's user
+   key; LGS_GET_NOTFOUND where nothing was found.
+   Returns LGS_ENOSPC with *out_needed = the bytes the results take when
+   out_cap is smaller (called and status are written then, out is not);
+   LGS_EINVAL for NULL or inconsistent arguments before any device work.
+   The index block is read and searched on the device; the handles it yields
+   come back to the host once to size the read of the distinct data blocks. */
+int lgs_table_get_host(const uint8_t *file, uint64_t file_len, int verify_checksums,
+                       int paranoid_checks, int internal_keys, const char *filter_name,
+                       const uint8_t *keys, const uint64_t *key_off, const uint32_t *key_len,
+                       uint32_t nq, uint8_t *called, uint8_t *status, uint8_t *verdict,
+                       uint8_t *out, size_t out_cap, uint64_t *out_key_off,
+                       uint64_t *out_val_off, size_t *out_needed);
+
 /* Devices and diagnostics. */
 /* The drop-in's current footprint: pinned and device bytes held by its
    staging slots, the number of slots created (all devices) and the bytes of

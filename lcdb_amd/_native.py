@@ -16,6 +16,7 @@ LGS_ST_CORRUPT, LGS_ST_OK, LGS_ST_NOSPACE = 0, 1, 2
 LGS_ST_IOERR, LGS_ST_BADCRC, LGS_ST_BADTYPE = 3, 4, 5
 LGS_NO_COMPRESSION, LGS_SNAPPY_COMPRESSION = 0, 1
 LGS_TRAILER_SIZE = 5
+LGS_GET_NOTFOUND, LGS_GET_FOUND, LGS_GET_DELETED, LGS_GET_CORRUPT = 0, 1, 2, 3
 
 _u8p = C.POINTER(C.c_uint8)
 _vp = C.c_void_p
@@ -76,6 +77,13 @@ _SIGS = {
     "lgs_table_build_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64,
                                        C.c_uint32, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t,
                                        C.POINTER(C.c_size_t)]),
+    "lgs_block_seek_scratch": (C.c_size_t, [C.c_uint32]),
+    "lgs_block_seek_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32,
+                                     C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     C.c_size_t, _vp]),
+    "lgs_table_get_host": (C.c_int, [_vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp,
+                                     _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_size_t, _vp,
+                                     _vp, C.POINTER(C.c_size_t)]),
     "lgs_dropin_footprint": (C.c_int, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                        C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]),
     "lgs_service_quiesce": (C.c_int, []),

@@ -39,12 +39,14 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/lcdb_gpu_snappy.h"
 
 #include "lgs_block.h"
 #include "lgs_launch.h"
+#include "lgs_seek.h"
 #include "lgs_table_tail.h"
 
 namespace lgs {
@@ -2690,6 +2692,374 @@ int lgs_table_build_host(const uint8_t* keys, const uint64_t* key_off, const uin
   LGS_HIP(hipMemcpyAsync(file, d + o_file, (size_t)end, hipMemcpyDeviceToHost, s));
   LGS_HIP(hipStreamSynchronize(s));
   tail_footer(file + end, thoff[0], thsize[0], thoff[1], thsize[1]);   // :346-362
+  return LGS_OK;
+}
+
+// ---- batched point lookups (kernels: lgs_seek.hip) ----
+
+size_t lgs_block_seek_scratch(uint32_t nq) { return align_up(4 * (size_t)nq, 256); }
+
+int lgs_block_seek_dev(const uint8_t* d_blocks, const uint64_t* d_block_off,
+                       const uint32_t* d_block_len, const uint8_t* d_block_status,
+                       uint32_t nblocks, const uint32_t* d_query_block, const uint8_t* d_keys,
+                       const uint64_t* d_key_off, const uint32_t* d_key_len, uint32_t nq,
+                       int internal_keys, uint32_t* d_entry_pos, uint32_t* d_found_key_len,
+                       uint32_t* d_val_pos, uint32_t* d_val_len, uint8_t* d_status,
+                       uint8_t* d_key_out, const uint64_t* d_key_out_off,
+                       const uint32_t* d_key_out_cap, void* d_scratch, size_t scratch_bytes,
+                       void* stream) {
+  if (nq == 0) return LGS_OK;
+  if ((nblocks && (!d_blocks || !d_block_off || !d_block_len)) || !d_query_block || !d_keys ||
+      !d_key_off || !d_key_len || !d_entry_pos || !d_found_key_len || !d_val_pos || !d_val_len ||
+      !d_status || !d_scratch || (d_key_out && (!d_key_out_off || !d_key_out_cap)))
+    return fail(LGS_EINVAL, "NULL argument");
+  if (internal_keys != 0 && internal_keys != 1)
+    return fail(LGS_EINVAL, "internal_keys must be 0 or 1");
+  if (scratch_bytes < lgs_block_seek_scratch(nq))
+    return fail(LGS_EINVAL, "scratch of %zu bytes, %zu needed", scratch_bytes,
+                lgs_block_seek_scratch(nq));
+  const SeekArgs a{d_blocks, d_block_off, d_block_len, d_block_status, nblocks, d_query_block,
+                   d_keys, d_key_off, d_key_len, nq, (uint32_t)internal_keys, d_entry_pos,
+                   d_found_key_len, d_val_pos, d_val_len, d_status, (uint32_t*)d_scratch,
+                   d_key_out, d_key_out_off, d_key_out_cap};
+  LGS_HIP(launch_block_seek(a, (hipStream_t)stream));
+  return LGS_OK;
+}
+
+namespace {
+
+// What the read path needs to know of one block handle before the launch:
+// whether its bytes and trailer lie inside the file, and the room its
+// contents take (the raw size, or a Snappy block's size header,
+// snappy.c:386-399).  A header beyond anything `size` bytes of Snappy can
+// expand to (64 bytes per 3-byte copy) cannot decode: the room is capped
+// there and the decoder's LGS_ST_NOSPACE stands for the reference's
+// "corrupted compressed block contents" (format.c:247-251).
+struct HandlePlan {
+  bool in_file = false;
+  uint32_t cap = 0;
+};
+
+int plan_handle(const uint8_t* file, uint64_t file_len, uint64_t off, uint64_t size,
+                HandlePlan* p) {
+  p->in_file = size <= ~0ull - LGS_TRAILER_SIZE && off <= file_len &&
+               file_len - off >= size + LGS_TRAILER_SIZE;
+  p->cap = 0;
+  if (!p->in_file) return LGS_OK;
+  if (size > 0x7fffffffull)
+    return fail(LGS_EINVAL, "a block of %llu bytes: under 2^31 supported", (unsigned long long)size);
+  p->cap = (uint32_t)size;
+  if (file[off + size] == LGS_SNAPPY_COMPRESSION) {
+    uint32_t want = 0;
+    const uint64_t most = 32 * size + 64;
+    p->cap = read_varint32(&want, file + off, (size_t)size) ? want : 0;
+    if (p->cap > most) p->cap = (uint32_t)most;
+  }
+  return LGS_OK;
+}
+
+struct HandleKey {
+  uint64_t off, size;
+  bool operator==(const HandleKey& o) const { return off == o.off && size == o.size; }
+};
+struct HandleHash {
+  size_t operator()(const HandleKey& k) const {
+    return (size_t)((k.off * 0x9e3779b97f4a7c15ull) ^ (k.size + (k.off >> 32)));
+  }
+};
+
+// Stages n handles for table_read: their byte ranges packed 16-aligned at
+// h_blk (lgs_table_read_host's layout: a handle outside the file points past
+// the image, so the device reports the truncated read), the handle arrays
+// and each block's 16-aligned output slot from out_base on.  Returns the
+// image's length; *out_end = the end of the slots.
+size_t stage_handles(const uint8_t* file, const uint64_t* off, const uint64_t* size,
+                     const HandlePlan* plan, uint32_t n, uint8_t* h_blk, uint64_t* hoff,
+                     uint64_t* hsize, uint64_t* ooff, uint32_t* ocap, size_t out_base,
+                     size_t* out_end) {
+  size_t ba = 0, oa = out_base;
+  for (uint32_t j = 0; j < n; ++j) {
+    hsize[j] = size[j];
+    hoff[j] = plan[j].in_file ? ba : ~0ull;
+    if (plan[j].in_file) ba += align_up((size_t)size[j] + LGS_TRAILER_SIZE, 16);
+    ooff[j] = oa;
+    ocap[j] = plan[j].cap;
+    oa += align_up(plan[j].cap, 16);
+  }
+  for (uint32_t j = 0; j < n; ++j)
+    if (hoff[j] == ~0ull) hoff[j] = ba + 16 + 1;
+  par_for(n, ba, [&](uint32_t j0, uint32_t j1) {
+    for (uint32_t j = j0; j < j1; ++j)
+      if (hoff[j] <= ba) memcpy(h_blk + hoff[j], file + off[j], (size_t)size[j] + LGS_TRAILER_SIZE);
+  });
+  *out_end = oa;
+  return ba;
+}
+
+size_t handles_image(const uint64_t* size, const HandlePlan* plan, uint32_t n, size_t* out_bytes,
+                     uint32_t* max_cap) {
+  size_t ba = 0, oa = 0;
+  uint32_t mc = 0;
+  for (uint32_t j = 0; j < n; ++j) {
+    if (plan[j].in_file) ba += align_up((size_t)size[j] + LGS_TRAILER_SIZE, 16);
+    oa += align_up(plan[j].cap, 16);
+    if (plan[j].cap > mc) mc = plan[j].cap;
+  }
+  *out_bytes = oa;
+  *max_cap = mc;
+  return ba;
+}
+
+}  // namespace
+
+int lgs_table_get_host(const uint8_t* file, uint64_t file_len, int verify_checksums,
+                       int paranoid_checks, int internal_keys, const char* filter_name,
+                       const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
+                       uint32_t nq, uint8_t* called, uint8_t* status, uint8_t* verdict,
+                       uint8_t* out, size_t out_cap, uint64_t* out_key_off,
+                       uint64_t* out_val_off, size_t* out_needed) {
+  if (!file || !out_needed || !out_key_off || !out_val_off)
+    return fail(LGS_EINVAL, "NULL argument");
+  if (internal_keys != 0 && internal_keys != 1)
+    return fail(LGS_EINVAL, "internal_keys must be 0 or 1");
+  *out_needed = 0;
+  out_key_off[0] = out_val_off[0] = 0;
+  if (nq == 0) return LGS_OK;
+  if (!keys || !key_off || !key_len || !called || !status || (out_cap && !out))
+    return fail(LGS_EINVAL, "NULL argument");
+  if (nq > kMaxEntries) return fail(LGS_EINVAL, "%u queries: under 2^31 supported", nq);
+  size_t kb = 0;
+  for (uint32_t q = 0; q < nq; ++q) kb += key_len[q];
+  // ldb_table_open on the host: footer and metaindex (before the lease: the
+  // metaindex read takes a context of its own).
+  uint64_t h2_off[2] = {0, 0}, h2_size[2] = {0, 0};
+  uint8_t open_st = LGS_ST_OK;
+  LGS_TRY(table_open(file, file_len, paranoid_checks, filter_name, &h2_off[0], &h2_size[0],
+                     &h2_off[1], &h2_size[1], &open_st));
+  auto all_fail = [&](uint8_t st) {
+    for (uint32_t q = 0; q < nq; ++q) {
+      called[q] = 0;
+      status[q] = st;
+      if (verdict) verdict[q] = kGetNotFound;
+      out_key_off[q + 1] = out_val_off[q + 1] = 0;
+    }
+    return LGS_OK;
+  };
+  if (open_st != LGS_ST_OK) return all_fail(open_st);
+  const bool want_filter = h2_off[1] != ~0ull;
+  const uint32_t n2 = want_filter ? 2u : 1u;
+  HandlePlan plan2[2];
+  for (uint32_t j = 0; j < n2; ++j)
+    LGS_TRY(plan_handle(file, file_len, h2_off[j], h2_size[j], &plan2[j]));
+  Lease lease(batch_pool());
+  LGS_TRY(lease.acquire());
+  Ctx& c = lease.ctx();
+  hipStream_t s = c.stream;
+
+  // -- A: index (and filter) block, the index seek, the handles, the filter.
+  size_t out2 = 0;
+  uint32_t max_cap2 = 0;
+  const size_t img2 = handles_image(h2_size, plan2, n2, &out2, &max_cap2);
+  const ReadScratch R2(n2);
+  Layout L;  // uploads | downloads | device-only
+  const size_t o_keys = L.take(kb + 16);
+  const size_t o_koff = L.take(8 * (size_t)nq);
+  const size_t o_klen = L.take(4 * (size_t)nq);
+  const size_t o_blk = L.take(img2 + 32);
+  const size_t o_hoff = L.take(16);
+  const size_t o_hsize = L.take(16);
+  const size_t o_ooff = L.take(16);
+  const size_t o_ocap = L.take(8);
+  const size_t o_zero = L.take(8);
+  const size_t up_end = L.at;
+  const size_t o_state = L.take(nq);           // downloads, contiguous
+  const size_t o_match = L.take(nq);
+  const size_t o_sst = L.take(nq);
+  const size_t o_qhoff = L.take(8 * (size_t)nq);
+  const size_t o_qhsize = L.take(8 * (size_t)nq);
+  const size_t o_bst = L.take(2);
+  const size_t down_end = L.at;
+  const size_t o_olen = L.take(8);
+  const size_t o_epos = L.take(4 * (size_t)nq);
+  const size_t o_fkl = L.take(4 * (size_t)nq);
+  const size_t o_vpos = L.take(4 * (size_t)nq);
+  const size_t o_vlen = L.take(4 * (size_t)nq);
+  const size_t o_rpos = L.take(lgs_block_seek_scratch(nq));
+  const size_t o_rscr = L.take(R2.total);
+  const size_t o_out2 = L.take(out2 + 16);
+  LGS_TRY(ctx_reserve(c, L.at, down_end));
+  uint8_t* h = c.h_buf;
+  uint8_t* d = c.d_buf;
+  {
+    uint64_t* koff = (uint64_t*)(h + o_koff);
+    uint32_t* klen = (uint32_t*)(h + o_klen);
+    size_t at = 0;
+    for (uint32_t q = 0; q < nq; ++q) {
+      koff[q] = at;
+      klen[q] = key_len[q];
+      at += key_len[q];
+    }
+    par_for(nq, kb, [&](uint32_t q0, uint32_t q1) {
+      for (uint32_t q = q0; q < q1; ++q) memcpy(h + o_keys + koff[q], keys + key_off[q], key_len[q]);
+    });
+    memset(h + o_keys + kb, 0, 16);
+    *(uint64_t*)(h + o_zero) = 0;
+  }
+  size_t out2_end = 0;
+  stage_handles(file, h2_off, h2_size, plan2, n2, h + o_blk, (uint64_t*)(h + o_hoff),
+                (uint64_t*)(h + o_hsize), (uint64_t*)(h + o_ooff), (uint32_t*)(h + o_ocap), o_out2,
+                &out2_end);
+  LGS_HIP(hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, s));
+  const uint8_t* d_keys = d + o_keys;
+  const uint64_t* d_koff = (const uint64_t*)(d + o_koff);
+  const uint32_t* d_klen = (const uint32_t*)(d + o_klen);
+  uint32_t* d_epos = (uint32_t*)(d + o_epos);
+  uint32_t* d_fkl = (uint32_t*)(d + o_fkl);
+  uint32_t* d_vpos = (uint32_t*)(d + o_vpos);
+  uint32_t* d_vlen = (uint32_t*)(d + o_vlen);
+  uint32_t* d_rpos = (uint32_t*)(d + o_rpos);
+  LGS_TRY(table_read(d + o_blk, img2 + 16, (const uint64_t*)(d + o_hoff),
+                     (const uint64_t*)(d + o_hsize), n2, paranoid_checks, d,
+                     (const uint64_t*)(d + o_ooff), (const uint32_t*)(d + o_ocap), max_cap2,
+                     (uint32_t*)(d + o_olen), d + o_bst, d + o_rscr, R2, s));
+  // The index block stays where the read put it: block 0 of the seek.
+  const SeekArgs ia{d + o_out2, (const uint64_t*)(d + o_zero), (const uint32_t*)(d + o_olen),
+                    d + o_bst, 1, nullptr, d_keys, d_koff, d_klen, nq, (uint32_t)internal_keys,
+                    d_epos, d_fkl, d_vpos, d_vlen, d + o_sst, d_rpos, nullptr, nullptr, nullptr};
+  LGS_HIP(launch_block_seek(ia, s));
+  LGS_HIP(launch_get_handles(d + o_out2, d_epos, d_vpos, d_vlen, nq, (uint64_t*)(d + o_qhoff),
+                             (uint64_t*)(d + o_qhsize), d + o_state, s));
+  if (want_filter) {
+    // The block's length as the host knows it; a filter block that does not
+    // read is dropped below (table.c:71-72), whatever was matched in it.
+    const size_t f_at = o_out2 + align_up(plan2[0].cap, 16);
+    LGS_HIP(launch_filter_block_match(d + f_at, plan2[1].cap, (const uint64_t*)(d + o_qhoff), d_keys,
+                                      d_koff, d_klen, internal_keys ? 8u : 0u, d + o_match, nq, s));
+  }
+  LGS_HIP(hipMemcpyAsync(h + o_state, d + o_state, down_end - o_state, hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipStreamSynchronize(s));   // the read-back that sizes and de-duplicates the block read
+
+  // -- B: the distinct data blocks the surviving queries name.
+  const bool filter = want_filter && h[o_bst + 1] == LGS_ST_OK;
+  std::vector<uint32_t> qblock(nq, kNoBlock);
+  std::vector<uint8_t> pre(nq, LGS_ST_OK);
+  std::vector<uint64_t> b_off, b_size;
+  {
+    const uint8_t* state = h + o_state;
+    const uint8_t* match = h + o_match;
+    const uint8_t* sst = h + o_sst;
+    const uint64_t* qho = (const uint64_t*)(h + o_qhoff);
+    const uint64_t* qhs = (const uint64_t*)(h + o_qhsize);
+    std::unordered_map<HandleKey, uint32_t, HandleHash> seen;
+    for (uint32_t q = 0; q < nq; ++q) {
+      if (state[q] == 0) {
+        pre[q] = sst[q];                                   // the index iterator's status
+      } else if (state[q] == 2) {
+        pre[q] = LGS_ST_CORRUPT;                           // table.c:244-245
+      } else if (!filter || match[q]) {
+        const HandleKey k{qho[q], qhs[q]};
+        auto it = seen.find(k);
+        if (it == seen.end()) {
+          it = seen.emplace(k, (uint32_t)b_off.size()).first;
+          b_off.push_back(k.off);
+          b_size.push_back(k.size);
+        }
+        qblock[q] = it->second;
+      }
+    }
+  }
+  const uint32_t nb = (uint32_t)b_off.size();
+  std::vector<HandlePlan> plan(nb);
+  for (uint32_t j = 0; j < nb; ++j)
+    LGS_TRY(plan_handle(file, file_len, b_off[j], b_size[j], &plan[j]));
+  size_t outb = 0;
+  uint32_t max_cap = 0;
+  const size_t img = handles_image(b_size.data(), plan.data(), nb, &outb, &max_cap);
+  const ReadScratch R(nb);
+  Layout B;  // uploads | downloads | device-only
+  const size_t p_blk = B.take(img + 32);
+  const size_t p_hoff = B.take(8 * (size_t)nb);
+  const size_t p_hsize = B.take(8 * (size_t)nb);
+  const size_t p_ooff = B.take(8 * (size_t)nb);
+  const size_t p_ocap = B.take(4 * (size_t)nb);
+  const size_t p_qblock = B.take(4 * (size_t)nq);
+  const size_t p_pre = B.take(nq);
+  const size_t pin_b = B.at;
+  const size_t p_koff = B.take(8 * ((size_t)nq + 1));
+  const size_t p_voff = B.take(8 * ((size_t)nq + 1));
+  const size_t p_called = B.take(nq);
+  const size_t p_fst = B.take(nq);
+  const size_t p_verdict = B.take(nq);
+  const size_t p_olen = B.take(4 * (size_t)nb);
+  const size_t p_bst = B.take(nb);
+  const size_t p_len = B.take(4 * (size_t)nq);
+  const size_t p_sst = B.take(nq);
+  const size_t p_vsrc = B.take(8 * (size_t)nq);
+  const size_t p_vn = B.take(4 * (size_t)nq);
+  const size_t p_part = B.take(8 * scan_parts(nq) + 8);
+  const size_t p_rscr = B.take(R.total);
+  const size_t p_out = B.take(outb + 16);
+  LGS_TRY(ctx_reserve(c, 0, pin_b));
+  h = c.h_buf;
+  Scratch arena(B.at, s);
+  if (arena.status() != hipSuccess)
+    return fail(LGS_ENOMEM, "%zu bytes of device memory for %u blocks: %s", B.at, nb,
+                hipGetErrorString(arena.status()));
+  uint8_t* e = (uint8_t*)arena.get();
+  size_t outb_end = 0;
+  stage_handles(file, b_off.data(), b_size.data(), plan.data(), nb, h + p_blk,
+                (uint64_t*)(h + p_hoff), (uint64_t*)(h + p_hsize), (uint64_t*)(h + p_ooff),
+                (uint32_t*)(h + p_ocap), p_out, &outb_end);
+  memcpy(h + p_qblock, qblock.data(), 4 * (size_t)nq);
+  memcpy(h + p_pre, pre.data(), nq);
+  LGS_HIP(hipMemcpyAsync(e, h, pin_b, hipMemcpyHostToDevice, s));
+  if (nb)
+    LGS_TRY(table_read(e + p_blk, img + 16, (const uint64_t*)(e + p_hoff),
+                       (const uint64_t*)(e + p_hsize), nb, verify_checksums, e,
+                       (const uint64_t*)(e + p_ooff), (const uint32_t*)(e + p_ocap), max_cap,
+                       (uint32_t*)(e + p_olen), e + p_bst, e + p_rscr, R, s));
+  const uint32_t* d_qblock = (const uint32_t*)(e + p_qblock);
+  const SeekArgs da{e, (const uint64_t*)(e + p_ooff), (const uint32_t*)(e + p_olen), e + p_bst, nb,
+                    d_qblock, d_keys, d_koff, d_klen, nq, (uint32_t)internal_keys, d_epos, d_fkl,
+                    d_vpos, d_vlen, e + p_sst, d_rpos, nullptr, nullptr, nullptr};
+  LGS_HIP(launch_block_seek(da, s));
+  LGS_HIP(launch_get_lens(d_qblock, e + p_pre, d_epos, d_fkl, d_vlen, e + p_sst, nq, e + p_called,
+                          e + p_fst, (uint32_t*)(e + p_len), s));
+  uint64_t* d_okoff = (uint64_t*)(e + p_koff);
+  LGS_HIP(launch_scan(2, nullptr, (const uint32_t*)(e + p_len), (uint64_t*)(e + p_part), 0, d_okoff,
+                      d_okoff + nq, nq, s));
+  LGS_HIP(hipMemcpyAsync(out_key_off, d_okoff, 8 * ((size_t)nq + 1), hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipMemcpyAsync(called, e + p_called, nq, hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipMemcpyAsync(status, e + p_fst, nq, hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipStreamSynchronize(s));
+  for (uint32_t q = 0; q < nq; ++q)
+    if (status[q] == LGS_ST_NOSPACE) status[q] = LGS_ST_CORRUPT;   // plan_handle's cap
+  const uint64_t total = out_key_off[nq];
+  *out_needed = (size_t)total;
+  if (total > out_cap)
+    return fail(LGS_ENOSPC, "results take %llu bytes, out_cap %zu", (unsigned long long)total,
+                out_cap);
+
+  // -- C: keys, values and verdicts into the packed output.
+  Scratch packed((size_t)total + 16, s);
+  if (packed.status() != hipSuccess)
+    return fail(LGS_ENOMEM, "%llu bytes of device memory for the results: %s",
+                (unsigned long long)total + 16, hipGetErrorString(packed.status()));
+  uint8_t* d_out = (uint8_t*)packed.get();
+  const bool want_verdict = verdict && internal_keys;
+  const GatherArgs ga{e, (const uint64_t*)(e + p_ooff), d_qblock, d_keys, d_koff, d_klen,
+                      e + p_called, d_epos, d_rpos, d_fkl, d_vpos, d_vlen, nq, d_out, d_okoff,
+                      (uint64_t*)(e + p_voff), (uint64_t*)(e + p_vsrc), (uint32_t*)(e + p_vn),
+                      want_verdict ? e + p_verdict : nullptr};
+  LGS_HIP(launch_get_gather(ga, s));
+  LGS_HIP(launch_pack(e, (const uint64_t*)(e + p_vsrc), (const uint32_t*)(e + p_vn), d_out,
+                      (const uint64_t*)(e + p_voff), nq, s));
+  if (total) LGS_HIP(hipMemcpyAsync(out, d_out, (size_t)total, hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipMemcpyAsync(out_val_off, e + p_voff, 8 * ((size_t)nq + 1), hipMemcpyDeviceToHost, s));
+  if (want_verdict)
+    LGS_HIP(hipMemcpyAsync(verdict, e + p_verdict, nq, hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipStreamSynchronize(s));
+  if (verdict && !internal_keys) memset(verdict, kGetNotFound, nq);
   return LGS_OK;
 }
 

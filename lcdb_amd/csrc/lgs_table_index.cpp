@@ -15,6 +15,7 @@
 #include "../../include/lcdb_gpu_snappy.h"
 
 #include "lgs_launch.h"
+#include "lgs_seek.h"
 
 namespace {
 
@@ -65,6 +66,17 @@ bool varint64(uint64_t* z, const uint8_t** p, size_t* n) {
 // format.c:66-80 (trailing bytes ignored).
 bool handle_import(uint64_t* off, uint64_t* size, const uint8_t* p, size_t n) {
   return varint64(off, &p, &n) && varint64(size, &p, &n);
+}
+
+// format.c:116-137: the 48-byte footer's two handles.
+bool footer_import(const uint8_t* f, uint64_t* mi_off, uint64_t* mi_size, uint64_t* ix_off,
+                   uint64_t* ix_size) {
+  uint64_t magic = 0;
+  for (int i = 7; i >= 0; --i) magic = (magic << 8) | f[kFooterSize - 8 + i];
+  const uint8_t* p = f;
+  size_t n = kFooterSize;
+  return magic == kTableMagic && varint64(mi_off, &p, &n) && varint64(mi_size, &p, &n) &&
+         varint64(ix_off, &p, &n) && varint64(ix_size, &p, &n);
 }
 
 // One block through the device read path: contents, or the read status.
@@ -129,6 +141,31 @@ uint8_t walk_block(const std::vector<uint8_t>& b, bool internal_keys, Visit visi
   }
 }
 
+// Filter handle: metaindex entry `filter_name` (table.c:78-120; errors there
+// are not propagated, :103-106).  The metaindex is sorted: the seek's hit is
+// the first key >= name, a match only if equal.
+int filter_handle(const uint8_t* file, uint64_t file_len, uint64_t mi_off, uint64_t mi_size,
+                  int paranoid_checks, const char* filter_name, uint64_t* filter_off,
+                  uint64_t* filter_size) {
+  std::vector<uint8_t> blk;
+  uint8_t st = 0;
+  const int rc = read_block(file, file_len, mi_off, mi_size, paranoid_checks != 0, &blk, &st);
+  if (rc != LGS_OK) return rc;
+  if (st != LGS_ST_OK) return LGS_OK;
+  const std::string name(filter_name);
+  bool done = false;
+  walk_block(blk, false, [&](const std::string& k, const uint8_t* v, size_t vn) {
+    if (done || k < name) return;
+    done = true;
+    uint64_t o, s;
+    if (k == name && handle_import(&o, &s, v, vn)) {
+      *filter_off = o;
+      *filter_size = s;
+    }
+  });
+  return LGS_OK;
+}
+
 }  // namespace
 
 extern "C" int lgs_table_index_host(const uint8_t* file, uint64_t file_len, int paranoid_checks,
@@ -151,14 +188,8 @@ extern "C" int lgs_table_index_host(const uint8_t* file, uint64_t file_len, int 
     *status = LGS_ST_CORRUPT;                             // "file is too short"
     return LGS_OK;
   }
-  const uint8_t* f = file + file_len - kFooterSize;
-  uint64_t magic = 0;
-  for (int i = 7; i >= 0; --i) magic = (magic << 8) | f[kFooterSize - 8 + i];
   uint64_t mi_off = 0, mi_size = 0, ix_off = 0, ix_size = 0;
-  const uint8_t* p = f;
-  size_t n = kFooterSize;
-  if (magic != kTableMagic || !varint64(&mi_off, &p, &n) || !varint64(&mi_size, &p, &n) ||
-      !varint64(&ix_off, &p, &n) || !varint64(&ix_size, &p, &n)) {
+  if (!footer_import(file + file_len - kFooterSize, &mi_off, &mi_size, &ix_off, &ix_size)) {
     *status = LGS_ST_CORRUPT;
     return LGS_OK;
   }
@@ -201,25 +232,29 @@ extern "C" int lgs_table_index_host(const uint8_t* file, uint64_t file_len, int 
   if (overflow)
     return lgs::set_error(LGS_ENOSPC, "more index entries than cap / keys_cap");
   *status = walk != LGS_ST_OK ? walk : (bad_handle ? (uint8_t)LGS_ST_CORRUPT : (uint8_t)LGS_ST_OK);
-  // Filter handle: metaindex entry `filter_name` (table.c:78-120; errors there
-  // are not propagated, :103-106).  The metaindex is sorted: the seek's hit is
-  // the first key >= name, a match only if equal.
-  if (filter_name) {
-    rc = read_block(file, file_len, mi_off, mi_size, paranoid_checks != 0, &blk, &st);
-    if (rc != LGS_OK) return rc;
-    if (st == LGS_ST_OK) {
-      const std::string name(filter_name);
-      bool done = false;
-      walk_block(blk, false, [&](const std::string& k, const uint8_t* v, size_t vn) {
-        if (done || k < name) return;
-        done = true;
-        uint64_t o, s;
-        if (k == name && handle_import(&o, &s, v, vn)) {
-          *filter_off = o;
-          *filter_size = s;
-        }
-      });
-    }
+  if (filter_name)
+    return filter_handle(file, file_len, mi_off, mi_size, paranoid_checks, filter_name, filter_off,
+                         filter_size);
+  return LGS_OK;
+}
+
+// The part of ldb_table_open that lgs_table_get_host needs on the host: the
+// footer's index handle and the metaindex's filter handle (~0 / 0: none).
+// *status as lgs_table_index_host gives it for a short file or a bad footer.
+int lgs::table_open(const uint8_t* file, uint64_t file_len, int paranoid_checks,
+                    const char* filter_name, uint64_t* index_off, uint64_t* index_size,
+                    uint64_t* filter_off, uint64_t* filter_size, uint8_t* status) {
+  *status = LGS_ST_OK;
+  *filter_off = ~0ull;
+  *filter_size = 0;
+  uint64_t mi_off = 0, mi_size = 0;
+  if (file_len < kFooterSize ||
+      !footer_import(file + file_len - kFooterSize, &mi_off, &mi_size, index_off, index_size)) {
+    *status = LGS_ST_CORRUPT;
+    return LGS_OK;
   }
+  if (filter_name)
+    return filter_handle(file, file_len, mi_off, mi_size, paranoid_checks, filter_name, filter_off,
+                         filter_size);
   return LGS_OK;
 }

@@ -15,6 +15,10 @@ the batched C ABI that does both for many blocks per launch
 * ``build_blocks``    -- ``ldb_tablegen_add``'s data blocks and index keys from
   sorted entries (src/table/table_builder.c:215-255, block_builder.c:91-158);
 * ``build_table_host`` -- the whole ``.ldb`` of ``ldb_tablegen_*`` (:215-365);
+* ``seek_blocks_host`` -- ``ldb_blockiter_seek`` for many (block, key) queries
+  (src/table/block.c:324-451);
+* ``get_host``        -- ``ldb_table_internal_get`` for many keys against one
+  table image (src/table/table.c:314-364);
 * ``index_host``      -- ``ldb_table_open``'s footer, index-block handles and
   metaindex filter handle (src/table/table.c:78-180), the handles the batched
   read takes.
@@ -28,7 +32,8 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _native
-from ._native import (LGS_NO_COMPRESSION, LGS_SNAPPY_COMPRESSION, LGS_ST_BADCRC,
+from ._native import (LGS_ENOSPC, LGS_GET_CORRUPT, LGS_GET_DELETED, LGS_GET_FOUND,
+                      LGS_GET_NOTFOUND, LGS_NO_COMPRESSION, LGS_SNAPPY_COMPRESSION, LGS_ST_BADCRC,
                       LGS_ST_BADTYPE, LGS_ST_CORRUPT, LGS_ST_IOERR, LGS_ST_NOSPACE, LGS_ST_OK,
                       LGS_TRAILER_SIZE, check)
 from .snappy import _stream_ptr
@@ -37,9 +42,10 @@ _L = _native.lib()
 
 __all__ = [
     "crc32c_batch", "write_blocks", "read_blocks", "write_blocks_host", "read_blocks_host",
-    "index_host", "FILTER_NAME", "build_blocks", "build_blocks_host", "build_table_host",
+    "index_host", "FILTER_NAME", "seek_blocks_host", "get_host", "build_blocks", "build_blocks_host", "build_table_host",
     "LGS_NO_COMPRESSION", "LGS_SNAPPY_COMPRESSION", "LGS_TRAILER_SIZE", "LGS_ST_OK",
     "LGS_ST_CORRUPT", "LGS_ST_NOSPACE", "LGS_ST_IOERR", "LGS_ST_BADCRC", "LGS_ST_BADTYPE",
+    "LGS_GET_NOTFOUND", "LGS_GET_FOUND", "LGS_GET_DELETED", "LGS_GET_CORRUPT",
 ]
 
 
@@ -319,3 +325,120 @@ def index_host(file, paranoid_checks: bool = False, internal_keys: bool = False,
     ks = [keys[int(koff[i]):int(koff[i + 1])].tobytes() for i in range(n)]
     fh = None if foff.value == (1 << 64) - 1 else (foff.value, fsize.value)
     return handles, ks, fh, st.value
+
+
+def _pack_keys(keys):
+    """(bytes + 16 spare, key_off u64, key_len u32) numpy arrays."""
+    n = len(keys)
+    klen = np.array([len(k) for k in keys], dtype=np.uint32)
+    koff = np.zeros(n, dtype=np.uint64)
+    if n:
+        koff[1:] = np.cumsum(klen[:-1], dtype=np.uint64)
+    buf = np.frombuffer(b"".join(keys) + b"\0" * 16, dtype=np.uint8)
+    return buf, koff, klen
+
+
+def seek_blocks_host(blocks: Sequence[bytes], queries, internal_keys: bool = False,
+                     block_status=None):
+    """ldb_blockiter_create + ldb_blockiter_seek for every query (block index,
+    key) against the decoded `blocks` (lgs_block_seek_dev on uploaded copies).
+
+    Returns ([(entry_pos, key, value) or None], status array)."""
+    torch = _torch()
+    nb, nq = len(blocks), len(queries)
+    if nq == 0:
+        return [], np.zeros(0, dtype=np.uint8)
+    dev = torch.device("cuda")
+    blen = np.array([len(b) for b in blocks], dtype=np.uint32)
+    boff = np.zeros(nb, dtype=np.uint64)
+    if nb:
+        boff[1:] = np.cumsum(blen[:-1], dtype=np.uint64)
+    bbuf = np.frombuffer(b"".join(blocks) + b"\0" * 16, dtype=np.uint8)
+    kbuf, koff, klen = _pack_keys([k for _, k in queries])
+    qb = np.array([b for b, _ in queries], dtype=np.uint32)
+
+    def up(a, dt):
+        return torch.from_numpy(a.view(dt).copy()).to(dev)
+
+    d_b, d_boff, d_blen = up(bbuf, np.uint8), up(boff, np.int64), up(blen, np.int32)
+    d_k, d_koff, d_klen = up(kbuf, np.uint8), up(koff, np.int64), up(klen, np.int32)
+    d_qb = up(qb, np.int32)
+    d_bst = None if block_status is None else up(np.asarray(block_status, dtype=np.uint8), np.uint8)
+    i32 = lambda: torch.empty(nq, dtype=torch.int32, device=dev)   # noqa: E731
+    d_pos, d_fkl, d_vpos, d_vlen = i32(), i32(), i32(), i32()
+    d_st = torch.empty(nq, dtype=torch.uint8, device=dev)
+    scr = torch.empty(max(int(_L.lgs_block_seek_scratch(nq)), 1), dtype=torch.uint8, device=dev)
+
+    def run(d_kout, d_kout_off, d_kout_cap):
+        check(_L.lgs_block_seek_dev(
+            d_b.data_ptr(), d_boff.data_ptr(), d_blen.data_ptr(),
+            d_bst.data_ptr() if d_bst is not None else None, nb, d_qb.data_ptr(), d_k.data_ptr(),
+            d_koff.data_ptr(), d_klen.data_ptr(), nq, 1 if internal_keys else 0, d_pos.data_ptr(),
+            d_fkl.data_ptr(), d_vpos.data_ptr(), d_vlen.data_ptr(), d_st.data_ptr(),
+            d_kout.data_ptr() if d_kout is not None else None,
+            d_kout_off.data_ptr() if d_kout is not None else None,
+            d_kout_cap.data_ptr() if d_kout is not None else None,
+            scr.data_ptr(), int(scr.numel()), None), "lgs_block_seek_dev")
+        torch.cuda.synchronize()
+
+    run(None, None, None)                     # the lengths, then the keys
+    fkl = d_fkl.cpu().numpy().view(np.uint32)
+    cap = fkl.copy()
+    ooff = np.zeros(nq, dtype=np.uint64)
+    ooff[1:] = np.cumsum(cap[:-1], dtype=np.uint64)
+    d_kout = torch.zeros(int(cap.astype(np.uint64).sum()) + 16, dtype=torch.uint8, device=dev)
+    run(d_kout, up(ooff, np.int64), up(cap, np.int32))
+    pos = d_pos.cpu().numpy().view(np.uint32)
+    vpos = d_vpos.cpu().numpy().view(np.uint32)
+    vlen = d_vlen.cpu().numpy().view(np.uint32)
+    st = d_st.cpu().numpy()
+    kout = d_kout.cpu().numpy()
+    res = []
+    for q in range(nq):
+        if pos[q] == 0xFFFFFFFF:
+            res.append(None)
+            continue
+        blk = blocks[int(qb[q])]
+        res.append((int(pos[q]), kout[int(ooff[q]):int(ooff[q]) + int(fkl[q])].tobytes(),
+                    blk[int(vpos[q]):int(vpos[q]) + int(vlen[q])]))
+    return res, st
+
+
+def get_host(file, keys: Sequence[bytes], verify: bool = True, paranoid_checks: bool = False,
+             internal_keys: bool = False, filter_name: str | None = FILTER_NAME,
+             out_cap: Optional[int] = None):
+    """ldb_table_internal_get for every key against one table image
+    (lgs_table_get_host).  Returns ([(key, value) or None], status, verdict)."""
+    import ctypes as C
+    raw = bytes(file)
+    img = np.frombuffer(raw + b"\0", dtype=np.uint8)
+    nq = len(keys)
+    kbuf, koff, klen = _pack_keys(list(keys))
+    called = np.zeros(max(nq, 1), dtype=np.uint8)
+    status = np.zeros(max(nq, 1), dtype=np.uint8)
+    verdict = np.zeros(max(nq, 1), dtype=np.uint8)
+    okoff = np.zeros(nq + 1, dtype=np.uint64)
+    ovoff = np.zeros(nq + 1, dtype=np.uint64)
+    need = C.c_size_t(0)
+    cap = int(out_cap) if out_cap is not None else max(4096, 128 * nq)
+    for attempt in range(2):
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        rc = _L.lgs_table_get_host(img.ctypes.data, len(raw), 1 if verify else 0,
+                                   1 if paranoid_checks else 0, 1 if internal_keys else 0,
+                                   filter_name.encode() if filter_name else None,
+                                   kbuf.ctypes.data, koff.ctypes.data, klen.ctypes.data, nq,
+                                   called.ctypes.data, status.ctypes.data, verdict.ctypes.data,
+                                   out.ctypes.data, cap, okoff.ctypes.data, ovoff.ctypes.data,
+                                   C.byref(need))
+        if rc != LGS_ENOSPC or attempt:
+            break
+        cap = need.value                       # one retry with the size it asked for
+    check(rc, "lgs_table_get_host")
+    res = []
+    for q in range(nq):
+        if not called[q]:
+            res.append(None)
+            continue
+        a, b, c = int(okoff[q]), int(ovoff[q]), int(okoff[q + 1])
+        res.append((out[a:b].tobytes(), out[b:c].tobytes()))
+    return res, status[:nq], verdict[:nq]
