@@ -475,7 +475,20 @@ int lgs_service_quiesce(void);
 int lgs_service_resume(void);
 
 /* Process-wide kernel choices (A/B and tests; the defaults pick by batch):
-     "decoder": "auto" | "ring" (lane-per-block) | "wave" (wave-per-block)
+     "decoder": "auto" | "ring" | "wave"
+                "auto": batches of >= 28 672 blocks take the lane-per-block
+                route, smaller ones the wave-per-block decoder; "ring" and
+                "wave" force one of the two for every batch size.  The
+                lane-per-block route is decode_pair_kernel: 64 blocks per
+                workgroup, a lane per block in each of two waves, one parsing
+                tags and refilling the input rings, one moving bytes and
+                flushing (outputs up to 16 MiB a block; larger ones go by
+                their size class).
+                A batch whose largest output is over the 4 KiB class is first
+                split by size class on the device ("split" below), under
+                "auto" and "ring" alike; the forced kernel then takes
+                the 4 KiB class only, and the 16 KiB class and the outputs
+                above it run their own decoders.
      "wide":    "walk"  (decoder of outputs over 16 KiB: the one-tag walk)
      "split":   "1" | "0"  (size-class split of mixed batches, see above)
      "service": "1" | "0"  (the drop-in's resident waves)

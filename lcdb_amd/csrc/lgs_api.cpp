@@ -1025,6 +1025,7 @@ Options& options_init() {
     Options* v = new Options;
     const char* dk = getenv("LGS_DECODE_KERNEL");
     if (dk && !strcmp(dk, "ring")) v->decoder = kDecRing;
+    if (dk && !strcmp(dk, "ring32")) v->decoder = kDecRing32;
     if (dk && !strcmp(dk, "wave")) v->decoder = kDecWave;
 #ifdef LGS_PROBE_DECODERS
     if (dk && !strcmp(dk, "chain")) v->decoder = kDecChain;
@@ -1136,6 +1137,7 @@ int lgs_set_option(const char* name, const char* value) {
   if (!strcmp(name, "decoder")) {
     if (!strcmp(value, "auto") || !*value) o.decoder = kDecAuto;
     else if (!strcmp(value, "ring")) o.decoder = kDecRing;
+    else if (!strcmp(value, "ring32")) o.decoder = kDecRing32;
     else if (!strcmp(value, "wave")) o.decoder = kDecWave;
 #ifdef LGS_PROBE_DECODERS
     else if (!strcmp(value, "chain")) o.decoder = kDecChain;

@@ -15,7 +15,8 @@ namespace lgs {
 // LGS_DECODE_KERNEL / LGS_NO_SPLIT, read once at load -- nothing on the
 // launch path reads the environment).
 enum DecodeKernel {
-  kDecAuto = 0, kDecRing = 1, kDecWave = 2, kDecQuad = 3, kDecOps = 4, kDecGroup = 5, kDecChain = 6
+  kDecAuto = 0, kDecRing = 1, kDecWave = 2, kDecQuad = 3, kDecOps = 4, kDecGroup = 5, kDecChain = 6,
+  kDecRing32 = 7   // the lane-per-block ring route through decode_ring_kernel<true, 32>
 };
 // Outputs over the 16 KiB class: the one-tag walk (default), or, in the
 // probe library, the trip decoder or the workgroup decoder.

@@ -47,6 +47,35 @@ __device__ __forceinline__ uint32_t lgs_ring_ph_value_(const uint32_t* ph, uint3
 #define LGS_RING_PH_ACTIVE 0
 #endif
 
+// ---- decode_pair_kernel trip phases (the same probe build) ----------------
+// Both roles stamp their own phases 0-4 and 7 (the barrier and loop test).
+// At the end the mover's lanes 0-8 write its sums and trip count into their
+// blocks' out_len entries, the walker's lanes 16-24 its own, after a barrier
+// behind the mover's drained stores (both waves execute PAIR_PH_END_*).
+#ifdef LGS_PROBE_RING_PHASES
+#define LGS_PAIR_PH_DECL LGS_RING_PH_DECL
+#define LGS_PAIR_PH(k) LGS_RING_PH(k)
+#define LGS_PAIR_PH_TRIP() LGS_RING_PH_TRIP()
+#define LGS_PAIR_PH_END_MOVER(ok, lane, ptr)                              \
+  do {                                                                    \
+    if ((ok) && (lane) <= 8) *(ptr) = lgs_ring_ph_value_(ph_, ph_trips_, (lane), 0u); \
+    __builtin_amdgcn_s_waitcnt(0x0f70);                                   \
+    pair_barrier();                                                       \
+  } while (0)
+#define LGS_PAIR_PH_END_WALKER(ok, lane, ptr)                             \
+  do {                                                                    \
+    pair_barrier();                                                       \
+    if ((ok) && (lane) >= 16 && (lane) <= 24)                             \
+      *(ptr) = lgs_ring_ph_value_(ph_, ph_trips_, (lane) - 16, 0u);       \
+  } while (0)
+#else
+#define LGS_PAIR_PH_DECL do {} while (0)
+#define LGS_PAIR_PH(k) do {} while (0)
+#define LGS_PAIR_PH_TRIP() do {} while (0)
+#define LGS_PAIR_PH_END_MOVER(ok, lane, ptr) do {} while (0)
+#define LGS_PAIR_PH_END_WALKER(ok, lane, ptr) do {} while (0)
+#endif
+
 #ifdef LGS_PROBE_TRIPCOUNT
 #define LGS_RING_TRIPS_DECL uint32_t trips_ = 0
 #define LGS_RING_TRIP() (++trips_)

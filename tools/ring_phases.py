@@ -10,6 +10,12 @@ Phases: 0 first-slot piece (before the wait), 1 the trip's vmcnt(0),
 s_memtime whose use waits for every outstanding LDS operation too, so LDS
 latency is charged to the phase whose operations are in flight at its end.
 
+The "ring" route is decode_pair_kernel now: its two roles stamp their own
+phases (PAIR_MOVER, PAIR_WALKER below), the mover's lanes 0-8 and the
+walker's lanes 16-24 of each 64-block workgroup write them.  With
+LGS_DECODE_KERNEL=ring32 the probe build runs decode_ring_kernel and the
+layout above.
+
 usage: python tools/ring_phases.py PROBE_SO [PRODUCT_SO]
 Prints one JSON line: per-phase cycles per wave (median over waves), per
 trip, the share of the wave's life, and the launch times of the probe and
@@ -24,6 +30,12 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["piece1", "wait_vmcnt", "landing", "flush", "parse1", "slot2", "refill_req", "loop_test"]
+# decode_pair_kernel (the "ring" route; LGS_DECODE_KERNEL=ring32 selects the
+# old kernel and the layout above): each role's phases 0-4, and 7 = from its
+# last stamp through the barrier to the top of the next trip, i.e. mostly the
+# wait for the other role.
+PAIR_MOVER = ["wait_vmcnt", "far_landing", "flush", "slot1", "slot2", "", "", "barrier"]
+PAIR_WALKER = ["wait_vmcnt", "refill_landing", "slot1", "slot2", "end_refill_req", "", "", "barrier"]
 
 
 def child(lib: str, phases: bool) -> dict:
@@ -51,7 +63,21 @@ def child(lib: str, phases: bool) -> dict:
             ts.append(e0.elapsed_time(e1) * 1000.0)
     res = {"lib": os.path.basename(lib), "decode_us_p50": float(np.median(ts)),
            "status_ok": bool((st == 1).all())}
-    if phases:
+    if phases and os.environ.get("LGS_DECODE_KERNEL") != "ring32":
+        # decode_pair_kernel: 64 blocks per workgroup; the mover's lanes 0-8
+        # and the walker's lanes 16-24 hold their role's sums and trip count.
+        v = out.len.cpu().numpy().astype(np.float64).reshape(-1, 64)
+        res["workgroups"] = int(v.shape[0])
+        for role, base, names in (("mover", 0, PAIR_MOVER), ("walker", 16, PAIR_WALKER)):
+            ph, trips = v[:, base:base + 8], v[:, base + 8]
+            med, t50 = np.median(ph, axis=0), float(np.median(trips))
+            res[role] = {
+                "trips_p50": t50, "life_cycles_p50": float(np.median(ph.sum(axis=1))),
+                "life_cycles_max": float(ph.sum(axis=1).max()),
+                "phase_cycles_per_trip": {n: round(float(x) / t50, 1)
+                                          for n, x in zip(names, med) if n},
+                "work_cycles_per_trip": round(float(med[:7].sum()) / t50, 1)}
+    elif phases:
         v = out.len.cpu().numpy().astype(np.float64).reshape(-1, 32)   # 32 blocks per wave
         ph = v[:, :8]
         trips = v[:, 8]
