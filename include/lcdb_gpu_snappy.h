@@ -455,6 +455,76 @@ int lgs_table_get_host(const uint8_t *file, uint64_t file_len, int verify_checks
                        uint8_t *out, size_t out_cap, uint64_t *out_key_off,
                        uint64_t *out_val_off, size_t *out_needed);
 
+/* ---- opened tables ----
+ *
+ * lgs_table_get_host opens the table on every call: it reads and decodes the
+ * index and filter blocks each time.  An opened table does that once, as
+ * ldb_table_open (table.c:120-180) does, and keeps on the device the decoded
+ * index block, its length and status, and the decoded filter block; gets then
+ * run against them as ldb_table_internal_get runs against an ldb_table_t.
+ *
+ * lgs_table_open_host: paranoid_checks, internal_keys and filter_name as for
+ * lgs_table_get_host.  resident = 0: `file` is borrowed and must stay valid
+ * and unchanged in its data blocks until lgs_table_close (a get stages the
+ * blocks it reads from it, as lgs_table_get_host does); resident = 1: the
+ * whole image is uploaded (16 bytes of slack after it) and `file` may be
+ * freed when the call returns.  A table that does not open (short file, bad
+ * footer, an index block that does not read) still returns LGS_OK and a
+ * handle, with *status = that status; every get on it answers as
+ * lgs_table_get_host does for such a table (called 0, that status, verdict
+ * LGS_GET_NOTFOUND, all offsets 0).  A filter block that does not read is
+ * dropped (table.c:71-72).  The handle belongs to the calling thread's device
+ * (lgs_set_device); a later call from a thread set to another device returns
+ * LGS_EINVAL.  A handle is read-only once open: any number of threads may
+ * call lgs_table_get / lgs_table_get_dev / lgs_table_info on it at once.
+ *
+ * lgs_table_close frees the resident memory on the stream it was allocated on
+ * and waits for that stream alone; no call of this group synchronises the
+ * whole device.  No get on the handle may be in flight.  NULL is a no-op.
+ *
+ * lgs_table_info: any output may be NULL.  *index_bytes / *filter_bytes: the
+ * decoded blocks' lengths (0: none); *device_bytes: the memory the handle
+ * holds on the device.
+ *
+ * lgs_table_get: lgs_table_get_host's contract, word for word, minus the open
+ * arguments.  Between the index seek and the block read it differs inside:
+ * the distinct blocks are numbered on the device, by the offset of the index
+ * entry a query found rather than by the (offset, size) that entry carries,
+ * in file order whatever the order of the queries; two index entries that
+ * carry the same handle are read as two blocks, which changes no per-query
+ * output.  One read-back of 32 bytes (the number of distinct blocks, the room
+ * their contents take, the largest room, an error flag) sizes the block read;
+ * a borrowed image's call also fetches the distinct handles to stage their
+ * byte ranges.  A Snappy block's room is capped at 2^32 - 16 bytes as well.
+ *
+ * lgs_table_get_dev: the same with the keys and every per-query result in
+ * device memory (d_out_key_off / d_out_val_off: nq + 1 each); *out_needed
+ * stays a host word.  Resident tables only: LGS_EINVAL otherwise.  d_keys
+ * must be readable 16 bytes past its end.  The work is queued on `stream`,
+ * which the call synchronises twice itself, to size the block read and to
+ * learn the results' total; the device outputs are complete on `stream` (not
+ * necessarily on the host) when it returns.  LGS_ENOSPC as above: d_called
+ * and d_status are written, d_out is not.  Scratch comes from the library's
+ * stream-ordered pool: per query 68 bytes, per byte of the decoded index block
+ * 12, then what the block read and the results take. */
+typedef struct lgs_table lgs_table;
+int lgs_table_open_host(const uint8_t *file, uint64_t file_len, int paranoid_checks,
+                        int internal_keys, const char *filter_name, int resident,
+                        lgs_table **table, uint8_t *status);
+void lgs_table_close(lgs_table *table);
+int lgs_table_info(const lgs_table *table, uint8_t *status, int *resident,
+                   uint64_t *index_bytes, uint64_t *filter_bytes, uint64_t *device_bytes);
+int lgs_table_get(lgs_table *table, int verify_checksums, const uint8_t *keys,
+                  const uint64_t *key_off, const uint32_t *key_len, uint32_t nq,
+                  uint8_t *called, uint8_t *status, uint8_t *verdict, uint8_t *out,
+                  size_t out_cap, uint64_t *out_key_off, uint64_t *out_val_off,
+                  size_t *out_needed);
+int lgs_table_get_dev(lgs_table *table, int verify_checksums, const uint8_t *d_keys,
+                      const uint64_t *d_key_off, const uint32_t *d_key_len, uint32_t nq,
+                      uint8_t *d_called, uint8_t *d_status, uint8_t *d_verdict,
+                      uint8_t *d_out, size_t out_cap, uint64_t *d_out_key_off,
+                      uint64_t *d_out_val_off, size_t *out_needed, void *stream);
+
 /* Devices and diagnostics. */
 /* The drop-in's current footprint: pinned and device bytes held by its
    staging slots, the number of slots created (all devices) and the bytes of

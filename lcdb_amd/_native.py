@@ -84,6 +84,16 @@ _SIGS = {
     "lgs_table_get_host": (C.c_int, [_vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_char_p, _vp,
                                      _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_size_t, _vp,
                                      _vp, C.POINTER(C.c_size_t)]),
+    "lgs_table_open_host": (C.c_int, [_vp, C.c_uint64, C.c_int, C.c_int, C.c_char_p, C.c_int,
+                                      C.POINTER(C.c_void_p), C.POINTER(C.c_uint8)]),
+    "lgs_table_close": (None, [_vp]),
+    "lgs_table_info": (C.c_int, [_vp, C.POINTER(C.c_uint8), C.POINTER(C.c_int),
+                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                 C.POINTER(C.c_uint64)]),
+    "lgs_table_get": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp,
+                                C.c_size_t, _vp, _vp, C.POINTER(C.c_size_t)]),
+    "lgs_table_get_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp,
+                                    C.c_size_t, _vp, _vp, C.POINTER(C.c_size_t), _vp]),
     "lgs_dropin_footprint": (C.c_int, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                        C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]),
     "lgs_service_quiesce": (C.c_int, []),

@@ -3065,6 +3065,492 @@ int lgs_table_get_host(const uint8_t* file, uint64_t file_len, int verify_checks
   return LGS_OK;
 }
 
+// ---- opened tables: ldb_table_open once, ldb_table_internal_get many times
+//  ----
+
+// Read-only after lgs_table_open_host: gets from several threads share it.
+struct lgs_table {
+  int device = -1;
+  uint8_t status = LGS_ST_OK;       // why the table did not open, else LGS_ST_OK
+  int resident = 0, internal = 0;
+  const uint8_t* file = nullptr;    // borrowed when not resident
+  uint64_t file_len = 0;
+  bool filter = false;              // a filter block that read
+  uint32_t index_len = 0;           // the decoded index block
+  uint32_t filter_len = 0;          // the filter block as the match takes it
+  uint32_t filter_bytes = 0;        // the decoded filter block
+  hipStream_t stream = nullptr;     // the stream `mem` was allocated on and is freed on
+  std::unique_ptr<Scratch> mem;     // index | filter | lengths | statuses | a zero | image
+  uint8_t* d = nullptr;
+  size_t d_bytes = 0;
+  size_t o_filter = 0, o_olen = 0, o_bst = 0, o_zero = 0, o_img = 0;   // the index block at 0
+};
+
+namespace {
+
+// Device scratch of one lgs_table_get / lgs_table_get_dev call before the
+// block read, from the library's pool on the call's stream:
+//   per query   1 + 1 + 1 + 1 (state, match, seek status, pre)
+//               + 8 + 8 (handle) + 5 * 4 (entry, key length, value, restart run)
+//               + 4 (qblock) + 8 + 8 + 4 + 4 (a distinct block's handle and room)
+//   per byte of the decoded index block   4 (mark) + 8 (rank)
+//   8 * scan_parts(max(nq, index_len)) + 8 + 32 (the scans' partial sums, info)
+// each array rounded up to 256 bytes; a host call adds its keys + 16 and 12
+// bytes a key.  The block read and the results take what lgs_table_get_host's
+// second half takes.
+struct GetScratch {
+  size_t keys = 0, koff = 0, klen = 0, up_end = 0;
+  size_t state, match, sst, pre, qhoff, qhsize, epos, fkl, vpos, vlen, rpos, qblock, boff, bsize,
+      ocap, room, info, mark, rank, part, total;
+  GetScratch(uint32_t nq, uint32_t index_len, bool host, size_t kb) {
+    Layout L;
+    if (host) {
+      keys = L.take(kb + 16);
+      koff = L.take(8 * (size_t)nq);
+      klen = L.take(4 * (size_t)nq);
+    }
+    up_end = L.at;
+    state = L.take(nq);
+    match = L.take(nq);
+    sst = L.take(nq);
+    pre = L.take(nq);
+    qhoff = L.take(8 * (size_t)nq);
+    qhsize = L.take(8 * (size_t)nq);
+    epos = L.take(4 * (size_t)nq);
+    fkl = L.take(4 * (size_t)nq);
+    vpos = L.take(4 * (size_t)nq);
+    vlen = L.take(4 * (size_t)nq);
+    rpos = L.take(lgs_block_seek_scratch(nq));
+    qblock = L.take(4 * (size_t)nq);
+    boff = L.take(8 * (size_t)nq);
+    bsize = L.take(8 * (size_t)nq);
+    ocap = L.take(4 * (size_t)nq);
+    room = L.take(4 * (size_t)nq);
+    info = L.take(32);
+    mark = L.take(4 * (size_t)index_len);
+    rank = L.take(8 * (size_t)index_len);
+    part = L.take(8 * scan_parts(nq > index_len ? nq : index_len) + 8);
+    total = L.at;
+  }
+};
+
+// Where a get's keys come from and where its results go: host memory
+// (lgs_table_get) or device memory (lgs_table_get_dev).
+struct GetIo {
+  bool dev;
+  const uint8_t* keys; const uint64_t* key_off; const uint32_t* key_len;
+  uint8_t* called; uint8_t* status; uint8_t* verdict; uint8_t* out; size_t out_cap;
+  uint64_t* out_key_off; uint64_t* out_val_off; size_t* out_needed;
+};
+
+int table_get(lgs_table* t, int verify_checksums, const GetIo& io, uint32_t nq,
+              hipStream_t user_stream) {
+  if (!t || !io.out_needed || !io.out_key_off || !io.out_val_off)
+    return fail(LGS_EINVAL, "NULL argument");
+  *io.out_needed = 0;
+  if (io.dev && !t->resident)
+    return fail(LGS_EINVAL, "lgs_table_get_dev needs a table opened with resident = 1");
+  int dev = -1;
+  LGS_TRY(call_device(&dev));
+  if (dev != t->device)
+    return fail(LGS_EINVAL, "table opened on device %d, call on device %d", t->device, dev);
+  if (io.dev) {
+    LGS_HIP(hipMemsetAsync(io.out_key_off, 0, 8, user_stream));
+    LGS_HIP(hipMemsetAsync(io.out_val_off, 0, 8, user_stream));
+  } else {
+    io.out_key_off[0] = io.out_val_off[0] = 0;
+  }
+  if (nq == 0) return LGS_OK;
+  if (!io.keys || !io.key_off || !io.key_len || !io.called || !io.status ||
+      (io.out_cap && !io.out))
+    return fail(LGS_EINVAL, "NULL argument");
+  if (nq > kMaxEntries) return fail(LGS_EINVAL, "%u queries: under 2^31 supported", nq);
+  if (t->status != LGS_ST_OK) {
+    if (io.dev) {
+      LGS_HIP(launch_get_fail(nq, t->status, io.called, io.status, io.verdict, io.out_key_off,
+                              io.out_val_off, user_stream));
+      return LGS_OK;
+    }
+    for (uint32_t q = 0; q < nq; ++q) {
+      io.called[q] = 0;
+      io.status[q] = t->status;
+      if (io.verdict) io.verdict[q] = kGetNotFound;
+      io.out_key_off[q + 1] = io.out_val_off[q + 1] = 0;
+    }
+    return LGS_OK;
+  }
+  size_t kb = 0;
+  if (!io.dev)
+    for (uint32_t q = 0; q < nq; ++q) kb += io.key_len[q];
+  Lease lease(batch_pool());
+  LGS_TRY(lease.acquire());
+  Ctx& c = lease.ctx();
+  hipStream_t s = io.dev ? user_stream : c.stream;
+  const uint32_t internal_keys = (uint32_t)t->internal;
+
+  // -- A: the index seek, the handles and the filter on the resident blocks;
+  // the live queries' entries marked, ranked and planned on the device.
+  const GetScratch G(nq, t->index_len, !io.dev, kb);
+  const size_t pin_info = G.up_end, pin_total = G.up_end + 32;
+  LGS_TRY(ctx_reserve(c, 0, G.up_end + 64));
+  uint8_t* h = c.h_buf;
+  Scratch first(G.total, s);
+  if (first.status() != hipSuccess)
+    return fail(LGS_ENOMEM, "%zu bytes of device memory for %u queries: %s", G.total, nq,
+                hipGetErrorString(first.status()));
+  uint8_t* d = (uint8_t*)first.get();
+  const uint8_t* d_keys = io.keys;
+  const uint64_t* d_koff = io.key_off;
+  const uint32_t* d_klen = io.key_len;
+  if (!io.dev) {
+    uint64_t* koff = (uint64_t*)(h + G.koff);
+    uint32_t* klen = (uint32_t*)(h + G.klen);
+    size_t at = 0;
+    for (uint32_t q = 0; q < nq; ++q) {
+      koff[q] = at;
+      klen[q] = io.key_len[q];
+      at += io.key_len[q];
+    }
+    par_for(nq, kb, [&](uint32_t q0, uint32_t q1) {
+      for (uint32_t q = q0; q < q1; ++q)
+        memcpy(h + G.keys + koff[q], io.keys + io.key_off[q], io.key_len[q]);
+    });
+    memset(h + G.keys + kb, 0, 16);
+    LGS_HIP(hipMemcpyAsync(d, h, G.up_end, hipMemcpyHostToDevice, s));
+    d_keys = d + G.keys;
+    d_koff = (const uint64_t*)(d + G.koff);
+    d_klen = (const uint32_t*)(d + G.klen);
+  }
+  uint32_t* d_epos = (uint32_t*)(d + G.epos);
+  uint32_t* d_fkl = (uint32_t*)(d + G.fkl);
+  uint32_t* d_vpos = (uint32_t*)(d + G.vpos);
+  uint32_t* d_vlen = (uint32_t*)(d + G.vlen);
+  uint32_t* d_rpos = (uint32_t*)(d + G.rpos);
+  uint32_t* d_qblock = (uint32_t*)(d + G.qblock);
+  uint64_t* d_boff = (uint64_t*)(d + G.boff);
+  uint64_t* d_bsize = (uint64_t*)(d + G.bsize);
+  uint32_t* d_ocap = (uint32_t*)(d + G.ocap);
+  uint64_t* d_info = (uint64_t*)(d + G.info);
+  LGS_HIP(hipMemsetAsync(d + G.info, 0, G.rank - G.info, s));   // info and the marks
+  const SeekArgs ia{t->d, (const uint64_t*)(t->d + t->o_zero), (const uint32_t*)(t->d + t->o_olen),
+                    t->d + t->o_bst, 1, nullptr, d_keys, d_koff, d_klen, nq, internal_keys,
+                    d_epos, d_fkl, d_vpos, d_vlen, d + G.sst, d_rpos, nullptr, nullptr, nullptr};
+  LGS_HIP(launch_block_seek(ia, s));
+  LGS_HIP(launch_get_handles(t->d, d_epos, d_vpos, d_vlen, nq, (uint64_t*)(d + G.qhoff),
+                             (uint64_t*)(d + G.qhsize), d + G.state, s));
+  if (t->filter)
+    LGS_HIP(launch_filter_block_match(t->d + t->o_filter, t->filter_len,
+                                      (const uint64_t*)(d + G.qhoff), d_keys, d_koff, d_klen,
+                                      internal_keys ? 8u : 0u, d + G.match, nq, s));
+  LGS_HIP(launch_live_mark(d + G.state, t->filter ? d + G.match : nullptr, d + G.sst, d_epos, nq,
+                           t->index_len, d + G.pre, d_qblock, (uint32_t*)(d + G.mark), s));
+  LGS_HIP(launch_scan(2, nullptr, (const uint32_t*)(d + G.mark), (uint64_t*)(d + G.part), 0,
+                      (uint64_t*)(d + G.rank), d_info, t->index_len, s));
+  LGS_HIP(launch_qblock((const uint64_t*)(d + G.rank), (const uint64_t*)(d + G.qhoff),
+                        (const uint64_t*)(d + G.qhsize), nq, d_qblock, d_boff, d_bsize, s));
+  if (t->resident)
+    LGS_HIP(launch_block_plan(t->d + t->o_img, t->file_len, d_boff, d_bsize,
+                              nq < t->index_len ? nq : t->index_len, d_ocap,
+                              (uint32_t*)(d + G.room), d_info, s));
+  LGS_HIP(hipMemcpyAsync(h + pin_info, d_info, 32, hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipStreamSynchronize(s));   // the one read-back that sizes the block read
+  const uint64_t* info = (const uint64_t*)(h + pin_info);
+  if (info[0] > nq)
+    return fail(LGS_EINTERNAL, "%llu distinct blocks for %u queries", (unsigned long long)info[0],
+                nq);
+  const uint32_t nb = (uint32_t)info[0];
+
+  // -- B: the distinct data blocks.
+  size_t outb = (size_t)info[1], img = 0;
+  uint32_t max_cap = (uint32_t)info[2];
+  std::vector<uint64_t> b_off, b_size;
+  std::vector<HandlePlan> plan;
+  if (t->resident) {
+    if (info[3])
+      return fail(LGS_EINVAL, "a block of 2^31 bytes or more: under 2^31 supported");
+  } else {
+    // The distinct handles come down: their byte ranges are staged from the
+    // borrowed image, as lgs_table_get_host stages them.
+    LGS_TRY(ctx_reserve(c, 0, 16 * (size_t)nb + 64));
+    h = c.h_buf;
+    if (nb) {
+      LGS_HIP(hipMemcpyAsync(h, d_boff, 8 * (size_t)nb, hipMemcpyDeviceToHost, s));
+      LGS_HIP(hipMemcpyAsync(h + 8 * (size_t)nb, d_bsize, 8 * (size_t)nb, hipMemcpyDeviceToHost,
+                             s));
+      LGS_HIP(hipStreamSynchronize(s));
+    }
+    const uint64_t* ho = (const uint64_t*)h;
+    b_off.assign(ho, ho + nb);
+    b_size.assign(ho + nb, ho + 2 * (size_t)nb);
+    plan.resize(nb);
+    for (uint32_t j = 0; j < nb; ++j)
+      LGS_TRY(plan_handle(t->file, t->file_len, b_off[j], b_size[j], &plan[j]));
+    img = handles_image(b_size.data(), plan.data(), nb, &outb, &max_cap);
+  }
+  const ReadScratch R(nb);
+  Layout B;  // uploads (a borrowed image only) | device-only
+  const size_t p_blk = B.take(t->resident ? 0 : img + 32);
+  const size_t p_hoff = B.take(8 * (size_t)nb);
+  const size_t p_hsize = B.take(8 * (size_t)nb);
+  const size_t p_ooff = B.take(8 * (size_t)nb);
+  const size_t p_ocap = B.take(4 * (size_t)nb);
+  const size_t pin_b = B.at;
+  const size_t p_koff = B.take(8 * ((size_t)nq + 1));
+  const size_t p_voff = B.take(8 * ((size_t)nq + 1));
+  const size_t p_called = B.take(nq);
+  const size_t p_fst = B.take(nq);
+  const size_t p_verdict = B.take(nq);
+  const size_t p_olen = B.take(4 * (size_t)nb);
+  const size_t p_bst = B.take(nb);
+  const size_t p_len = B.take(4 * (size_t)nq);
+  const size_t p_sst = B.take(nq);
+  const size_t p_vsrc = B.take(8 * (size_t)nq);
+  const size_t p_vn = B.take(4 * (size_t)nq);
+  const size_t p_part = B.take(8 * scan_parts(nq > nb ? nq : nb) + 8);
+  const size_t p_rscr = B.take(R.total);
+  const size_t p_out = B.take(outb + 16);
+  Scratch arena(B.at, s);
+  if (arena.status() != hipSuccess)
+    return fail(LGS_ENOMEM, "%zu bytes of device memory for %u blocks: %s", B.at, nb,
+                hipGetErrorString(arena.status()));
+  uint8_t* e = (uint8_t*)arena.get();
+  if (t->resident) {
+    LGS_HIP(launch_scan(2, nullptr, (const uint32_t*)(d + G.room), (uint64_t*)(e + p_part), p_out,
+                        (uint64_t*)(e + p_ooff), nullptr, nb, s));
+    if (nb)
+      LGS_TRY(table_read(t->d + t->o_img, t->file_len, d_boff, d_bsize, nb, verify_checksums, e,
+                         (const uint64_t*)(e + p_ooff), d_ocap, max_cap, (uint32_t*)(e + p_olen),
+                         e + p_bst, e + p_rscr, R, s));
+  } else {
+    LGS_TRY(ctx_reserve(c, 0, pin_b + 64));
+    h = c.h_buf;
+    size_t outb_end = 0;
+    stage_handles(t->file, b_off.data(), b_size.data(), plan.data(), nb, h + p_blk,
+                  (uint64_t*)(h + p_hoff), (uint64_t*)(h + p_hsize), (uint64_t*)(h + p_ooff),
+                  (uint32_t*)(h + p_ocap), p_out, &outb_end);
+    LGS_HIP(hipMemcpyAsync(e, h, pin_b, hipMemcpyHostToDevice, s));
+    if (nb)
+      LGS_TRY(table_read(e + p_blk, img + 16, (const uint64_t*)(e + p_hoff),
+                         (const uint64_t*)(e + p_hsize), nb, verify_checksums, e,
+                         (const uint64_t*)(e + p_ooff), (const uint32_t*)(e + p_ocap), max_cap,
+                         (uint32_t*)(e + p_olen), e + p_bst, e + p_rscr, R, s));
+  }
+  const SeekArgs da{e, (const uint64_t*)(e + p_ooff), (const uint32_t*)(e + p_olen), e + p_bst, nb,
+                    d_qblock, d_keys, d_koff, d_klen, nq, internal_keys, d_epos, d_fkl, d_vpos,
+                    d_vlen, e + p_sst, d_rpos, nullptr, nullptr, nullptr};
+  LGS_HIP(launch_block_seek(da, s));
+  uint8_t* d_called = io.dev ? io.called : e + p_called;
+  uint8_t* d_fst = io.dev ? io.status : e + p_fst;
+  LGS_HIP(launch_get_lens(d_qblock, d + G.pre, d_epos, d_fkl, d_vlen, e + p_sst, nq, d_called,
+                          d_fst, (uint32_t*)(e + p_len), s));
+  LGS_HIP(launch_nospace_is_corrupt(d_fst, nq, s));                // plan_handle's cap
+  uint64_t* d_okoff = io.dev ? io.out_key_off : (uint64_t*)(e + p_koff);
+  uint64_t* d_ovoff = io.dev ? io.out_val_off : (uint64_t*)(e + p_voff);
+  LGS_HIP(launch_scan(2, nullptr, (const uint32_t*)(e + p_len), (uint64_t*)(e + p_part), 0, d_okoff,
+                      d_okoff + nq, nq, s));
+  uint64_t total = 0;
+  if (io.dev) {
+    h = c.h_buf;
+    LGS_HIP(hipMemcpyAsync(h + pin_total, d_okoff + nq, 8, hipMemcpyDeviceToHost, s));
+    LGS_HIP(hipStreamSynchronize(s));
+    total = *(const uint64_t*)(h + pin_total);
+  } else {
+    LGS_HIP(hipMemcpyAsync(io.out_key_off, d_okoff, 8 * ((size_t)nq + 1), hipMemcpyDeviceToHost,
+                           s));
+    LGS_HIP(hipMemcpyAsync(io.called, d_called, nq, hipMemcpyDeviceToHost, s));
+    LGS_HIP(hipMemcpyAsync(io.status, d_fst, nq, hipMemcpyDeviceToHost, s));
+    LGS_HIP(hipStreamSynchronize(s));
+    total = io.out_key_off[nq];
+  }
+  *io.out_needed = (size_t)total;
+  if (total > io.out_cap)
+    return fail(LGS_ENOSPC, "results take %llu bytes, out_cap %zu", (unsigned long long)total,
+                io.out_cap);
+
+  // -- C: keys, values and verdicts into the packed output.
+  std::unique_ptr<Scratch> packed;
+  uint8_t* d_out = io.out;
+  if (!io.dev) {
+    packed.reset(new Scratch((size_t)total + 16, s));
+    if (packed->status() != hipSuccess)
+      return fail(LGS_ENOMEM, "%llu bytes of device memory for the results: %s",
+                  (unsigned long long)total + 16, hipGetErrorString(packed->status()));
+    d_out = (uint8_t*)packed->get();
+  }
+  const bool want_verdict = io.verdict && internal_keys;
+  uint8_t* d_verdict = io.dev ? io.verdict : e + p_verdict;
+  const GatherArgs ga{e, (const uint64_t*)(e + p_ooff), d_qblock, d_keys, d_koff, d_klen, d_called,
+                      d_epos, d_rpos, d_fkl, d_vpos, d_vlen, nq, d_out, d_okoff, d_ovoff,
+                      (uint64_t*)(e + p_vsrc), (uint32_t*)(e + p_vn),
+                      want_verdict ? d_verdict : nullptr};
+  LGS_HIP(launch_get_gather(ga, s));
+  if (total)
+    LGS_HIP(launch_pack(e, (const uint64_t*)(e + p_vsrc), (const uint32_t*)(e + p_vn), d_out,
+                        d_ovoff, nq, s));
+  if (io.dev) {
+    // The scratch is freed on the stream behind the work that uses it.
+    if (io.verdict && !internal_keys) LGS_HIP(hipMemsetAsync(io.verdict, kGetNotFound, nq, s));
+    return LGS_OK;
+  }
+  if (total) LGS_HIP(hipMemcpyAsync(io.out, d_out, (size_t)total, hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipMemcpyAsync(io.out_val_off, d_ovoff, 8 * ((size_t)nq + 1), hipMemcpyDeviceToHost, s));
+  if (want_verdict) LGS_HIP(hipMemcpyAsync(io.verdict, d_verdict, nq, hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipStreamSynchronize(s));
+  if (io.verdict && !internal_keys) memset(io.verdict, kGetNotFound, nq);
+  return LGS_OK;
+}
+
+void table_free(lgs_table* t) {
+  if (!t->mem) return;
+  int cur = -1;
+  const bool moved = hipGetDevice(&cur) == hipSuccess && cur != t->device &&
+                     hipSetDevice(t->device) == hipSuccess;
+  (void)t->mem->release();                 // stream-ordered, then that stream alone is waited on
+  (void)hipStreamSynchronize(t->stream);
+  t->mem.reset();
+  t->d = nullptr;
+  if (moved) (void)hipSetDevice(cur);
+}
+
+}  // namespace
+
+int lgs_table_open_host(const uint8_t* file, uint64_t file_len, int paranoid_checks,
+                        int internal_keys, const char* filter_name, int resident,
+                        lgs_table** table, uint8_t* status) {
+  if (!table || !status || !file) return fail(LGS_EINVAL, "NULL argument");
+  *table = nullptr;
+  if (internal_keys != 0 && internal_keys != 1)
+    return fail(LGS_EINVAL, "internal_keys must be 0 or 1");
+  if (resident != 0 && resident != 1) return fail(LGS_EINVAL, "resident must be 0 or 1");
+  int dev = -1;
+  LGS_TRY(call_device(&dev));
+  std::unique_ptr<lgs_table> t(new lgs_table);
+  t->device = dev;
+  t->resident = resident;
+  t->internal = internal_keys;
+  t->file = resident ? nullptr : file;
+  t->file_len = file_len;
+  // ldb_table_open on the host: footer and metaindex.
+  uint64_t h2_off[2] = {0, 0}, h2_size[2] = {0, 0};
+  uint8_t open_st = LGS_ST_OK;
+  LGS_TRY(table_open(file, file_len, paranoid_checks, filter_name, &h2_off[0], &h2_size[0],
+                     &h2_off[1], &h2_size[1], &open_st));
+  if (open_st != LGS_ST_OK) {
+    *status = t->status = open_st;
+    *table = t.release();
+    return LGS_OK;
+  }
+  const bool want_filter = h2_off[1] != ~0ull;
+  const uint32_t n2 = want_filter ? 2u : 1u;
+  HandlePlan plan2[2];
+  for (uint32_t j = 0; j < n2; ++j)
+    LGS_TRY(plan_handle(file, file_len, h2_off[j], h2_size[j], &plan2[j]));
+  Lease lease(batch_pool());
+  LGS_TRY(lease.acquire());
+  Ctx& c = lease.ctx();
+  hipStream_t s = c.stream;
+  // The index and filter block through table_read, once; what it leaves
+  // stays: the decoded blocks, their lengths and statuses.
+  size_t out2 = 0;
+  uint32_t max_cap2 = 0;
+  const size_t img2 = handles_image(h2_size, plan2, n2, &out2, &max_cap2);
+  const ReadScratch R2(n2);
+  Layout L;  // uploads | device-only
+  const size_t o_blk = L.take(img2 + 32);
+  const size_t o_hoff = L.take(16);
+  const size_t o_hsize = L.take(16);
+  const size_t o_ooff = L.take(16);
+  const size_t o_ocap = L.take(8);
+  const size_t up_end = L.at;
+  const size_t o_rscr = L.take(R2.total);
+  Layout T;
+  T.take(out2 + 16);
+  t->o_filter = align_up(plan2[0].cap, 16);
+  t->o_olen = T.take(8);
+  t->o_bst = T.take(2);
+  t->o_zero = T.take(8);
+  t->o_img = T.take(resident ? (size_t)file_len + 16 : 0);
+  t->d_bytes = T.at;
+  LGS_TRY(ctx_reserve(c, 0, up_end + 64));
+  uint8_t* h = c.h_buf;
+  t->stream = s;
+  t->mem.reset(new Scratch(t->d_bytes, s));
+  Scratch stage(L.at, s);
+  if (t->mem->status() != hipSuccess || stage.status() != hipSuccess)
+    return fail(LGS_ENOMEM, "%zu bytes of device memory for the opened table", t->d_bytes + L.at);
+  t->d = (uint8_t*)t->mem->get();
+  uint8_t* d = (uint8_t*)stage.get();
+  size_t out2_end = 0;
+  stage_handles(file, h2_off, h2_size, plan2, n2, h + o_blk, (uint64_t*)(h + o_hoff),
+                (uint64_t*)(h + o_hsize), (uint64_t*)(h + o_ooff), (uint32_t*)(h + o_ocap), 0,
+                &out2_end);
+  LGS_HIP(hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, s));
+  LGS_HIP(hipMemsetAsync(t->d + t->o_olen, 0, t->o_img - t->o_olen, s));
+  if (resident) {
+    if (file_len) LGS_HIP(hipMemcpyAsync(t->d + t->o_img, file, (size_t)file_len,
+                                         hipMemcpyHostToDevice, s));
+    LGS_HIP(hipMemsetAsync(t->d + t->o_img + file_len, 0, 16, s));
+  }
+  LGS_TRY(table_read(d + o_blk, img2 + 16, (const uint64_t*)(d + o_hoff),
+                     (const uint64_t*)(d + o_hsize), n2, paranoid_checks, t->d,
+                     (const uint64_t*)(d + o_ooff), (const uint32_t*)(d + o_ocap), max_cap2,
+                     (uint32_t*)(t->d + t->o_olen), t->d + t->o_bst, d + o_rscr, R2, s));
+  LGS_HIP(hipMemcpyAsync(h + up_end, t->d + t->o_olen, 8, hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipMemcpyAsync(h + up_end + 8, t->d + t->o_bst, 2, hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipStreamSynchronize(s));
+  const uint32_t* olen = (const uint32_t*)(h + up_end);
+  const uint8_t* bst = h + up_end + 8;
+  if (bst[0] != LGS_ST_OK) {
+    // An index block that does not read: its status for every lookup.
+    t->status = bst[0] == LGS_ST_NOSPACE ? (uint8_t)LGS_ST_CORRUPT : bst[0];
+    table_free(t.get());
+  } else {
+    t->index_len = olen[0];
+    t->filter = want_filter && bst[1] == LGS_ST_OK;      // table.c:71-72
+    t->filter_len = want_filter ? plan2[1].cap : 0;
+    t->filter_bytes = t->filter ? olen[1] : 0;
+  }
+  *status = t->status;
+  *table = t.release();
+  return LGS_OK;
+}
+
+void lgs_table_close(lgs_table* table) {
+  if (!table) return;
+  table_free(table);
+  delete table;
+}
+
+int lgs_table_info(const lgs_table* table, uint8_t* status, int* resident, uint64_t* index_bytes,
+                   uint64_t* filter_bytes, uint64_t* device_bytes) {
+  if (!table) return fail(LGS_EINVAL, "NULL argument");
+  if (status) *status = table->status;
+  if (resident) *resident = table->resident;
+  if (index_bytes) *index_bytes = table->index_len;
+  if (filter_bytes) *filter_bytes = table->filter_bytes;
+  if (device_bytes) *device_bytes = table->mem ? table->d_bytes : 0;
+  return LGS_OK;
+}
+
+int lgs_table_get(lgs_table* table, int verify_checksums, const uint8_t* keys,
+                  const uint64_t* key_off, const uint32_t* key_len, uint32_t nq, uint8_t* called,
+                  uint8_t* status, uint8_t* verdict, uint8_t* out, size_t out_cap,
+                  uint64_t* out_key_off, uint64_t* out_val_off, size_t* out_needed) {
+  const GetIo io{false, keys, key_off, key_len, called, status, verdict, out, out_cap,
+                 out_key_off, out_val_off, out_needed};
+  return table_get(table, verify_checksums, io, nq, nullptr);
+}
+
+int lgs_table_get_dev(lgs_table* table, int verify_checksums, const uint8_t* d_keys,
+                      const uint64_t* d_key_off, const uint32_t* d_key_len, uint32_t nq,
+                      uint8_t* d_called, uint8_t* d_status, uint8_t* d_verdict, uint8_t* d_out,
+                      size_t out_cap, uint64_t* d_out_key_off, uint64_t* d_out_val_off,
+                      size_t* out_needed, void* stream) {
+  const GetIo io{true, d_keys, d_key_off, d_key_len, d_called, d_status, d_verdict, d_out, out_cap,
+                 d_out_key_off, d_out_val_off, out_needed};
+  return table_get(table, verify_checksums, io, nq, (hipStream_t)stream);
+}
+
 int lgs_device_count(void) { return visible_devices(); }
 
 int lgs_set_device(int device) {

@@ -58,6 +58,52 @@ struct GatherArgs {
 };
 hipError_t launch_get_gather(const GatherArgs& a, hipStream_t s);
 
+// ---- the opened table's Get (lgs_table_get, lgs_table_get_dev) ----
+//
+// The distinct blocks of a batch are numbered on the device.  The key is the
+// offset of the index entry a query found, not the (offset, size) its value
+// decodes to: entries are marked in an array as long as the index block, an
+// exclusive scan of the marks ranks them in file order, and two entries that
+// carry the same handle count as two blocks.
+
+constexpr uint64_t kTrailerBytes = 5;           // LGS_TRAILER_SIZE
+constexpr uint32_t kMaxRoom = 0xfffffff0u;      // the largest 16-aligned room of one block
+
+// pre[q] as lgs_table_get_host's host loop sets it (state 0: the index seek's
+// status; 2: corrupt; a filter miss: OK); qblock[q] = the found entry's offset
+// for a live query (state 1 and match == null or match[q]), kNoBlock
+// otherwise; mark[that offset] = 1.  mark: index_len u32, zeroed beforehand.
+hipError_t launch_live_mark(const uint8_t* state, const uint8_t* match, const uint8_t* seek_status,
+                            const uint32_t* entry_pos, uint32_t nq, uint32_t index_len,
+                            uint8_t* pre, uint32_t* qblock, uint32_t* mark, hipStream_t s);
+
+// After launch_scan(2, ..) of mark into rank: qblock[q] = the rank of the
+// entry it held, and that block's handle (get_handles' hoff, hsize of any of
+// its queries) at b_off / b_size[rank].
+hipError_t launch_qblock(const uint64_t* rank, const uint64_t* hoff, const uint64_t* hsize,
+                         uint32_t nq, uint32_t* qblock, uint64_t* b_off, uint64_t* b_size,
+                         hipStream_t s);
+
+// Per distinct block j < info[0] (at most `bound`) of the resident image
+// file[0, file_len) (+ 16 readable bytes): out_cap[j] = the room its contents
+// take (the raw size; a Snappy block's size header, at most 32 * size + 64 and
+// kMaxRoom, 0 if it does not parse; 0 for a handle outside the file) and
+// room[j] = that, 16-aligned.  info (4 u64, [1..3] zeroed beforehand):
+// [1] += the rooms, [2] = their maximum, [3] |= 1 for a handle of 2^31 bytes
+// or more inside the file.
+hipError_t launch_block_plan(const uint8_t* file, uint64_t file_len, const uint64_t* b_off,
+                             const uint64_t* b_size, uint32_t bound, uint32_t* out_cap,
+                             uint32_t* room, uint64_t* info, hipStream_t s);
+
+// A table that did not open: called 0, status st, verdict (may be null)
+// kGetNotFound, nq + 1 zero offsets each.
+hipError_t launch_get_fail(uint32_t nq, uint8_t st, uint8_t* called, uint8_t* status,
+                           uint8_t* verdict, uint64_t* out_key_off, uint64_t* out_val_off,
+                           hipStream_t s);
+
+// kStNoSpace -> kStCorrupt in status[0, nq).
+hipError_t launch_nospace_is_corrupt(uint8_t* status, uint32_t nq, hipStream_t s);
+
 // Host (lgs_table_index.cpp): the footer's index handle and the metaindex's
 // filter handle (~0 / 0: none) of a table image; *status = LGS_ST_CORRUPT for
 // a short file or a bad footer.

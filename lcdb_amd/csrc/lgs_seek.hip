@@ -346,7 +346,172 @@ __global__ __launch_bounds__(256) void get_gather_kernel(GatherArgs a) {
   if (a.verdict) a.verdict[q] = verdict;
 }
 
+// ---- the opened table's Get: de-duplication on the device ----------------
+//
+// All a lane per item over coalesced 1-, 4- and 8-byte arrays; only
+// block_plan_kernel's two loads per block (type byte, size header) are
+// scattered.
+
+// table.c:345-352 before the block read, as lgs_table_get_host's host loop
+// has it: pre[q] for a query that reads no block, and for a live one (a
+// handle, and no filter or a filter match) a mark on the index entry it
+// found.  qblock[q] holds that entry's offset until qblock_kernel.
+__global__ __launch_bounds__(256) void live_mark_kernel(
+    const uint8_t* __restrict__ state, const uint8_t* __restrict__ match,
+    const uint8_t* __restrict__ seek_status, const uint32_t* __restrict__ entry_pos, uint32_t nq,
+    uint32_t index_len, uint8_t* __restrict__ pre, uint32_t* __restrict__ qblock,
+    uint32_t* __restrict__ mark) {
+  const uint32_t q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= nq) return;
+  const uint32_t st = state[q], pos = entry_pos[q];
+  uint32_t p = kStOk;
+  bool live = false;
+  if (st == 0) {
+    p = seek_status[q];                                    // the index iterator's status
+  } else if (st == 2) {
+    p = kStCorrupt;                                        // table.c:244-245
+  } else {
+    live = (!match || match[q]) && pos < index_len;
+  }
+  pre[q] = (uint8_t)p;
+  qblock[q] = live ? pos : kNoBlock;
+  if (live) mark[pos] = 1u;
+}
+
+// rank: the exclusive scan of the marks, so a marked entry's rank is its
+// block's number, in file order.  Every query of a block writes the block's
+// handle; they all found the same entry, so they write the same two words.
+__global__ __launch_bounds__(256) void qblock_kernel(
+    const uint64_t* __restrict__ rank, const uint64_t* __restrict__ hoff,
+    const uint64_t* __restrict__ hsize, uint32_t nq, uint32_t* __restrict__ qblock,
+    uint64_t* __restrict__ b_off, uint64_t* __restrict__ b_size) {
+  const uint32_t q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= nq) return;
+  const uint32_t pos = qblock[q];
+  if (pos == kNoBlock) return;
+  const uint32_t b = (uint32_t)rank[pos];
+  qblock[q] = b;
+  b_off[b] = hoff[q];
+  b_size[b] = hsize[q];
+}
+
+// plan_handle (lgs_api.cpp) per distinct block of a resident image: the room
+// its contents take, 0 for a handle outside the file.  info: {nb (read),
+// += the 16-aligned rooms, max= the rooms, |= 1 for a block of 2^31 bytes
+// or more}, one atomic each per workgroup.
+__global__ __launch_bounds__(256) void block_plan_kernel(
+    const uint8_t* __restrict__ file, uint64_t file_len, const uint64_t* __restrict__ b_off,
+    const uint64_t* __restrict__ b_size, uint32_t bound, uint32_t* __restrict__ out_cap,
+    uint32_t* __restrict__ room, uint64_t* __restrict__ info) {
+  __shared__ uint64_t s_sum;
+  __shared__ uint32_t s_max, s_err;
+  if (threadIdx.x == 0) {
+    s_sum = 0;
+    s_max = 0;
+    s_err = 0;
+  }
+  __syncthreads();
+  const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+  const uint64_t nb = info[0];
+  if (j < bound && j < nb) {
+    const uint64_t off = b_off[j], size = b_size[j];
+    const bool in_file = size <= ~0ull - kTrailerBytes && off <= file_len &&
+                         file_len - off >= size + kTrailerBytes;
+    uint32_t cap = 0;
+    if (in_file && size > 0x7fffffffull) {
+      atomicOr(&s_err, 1u);
+    } else if (in_file) {
+      const bytes_g p = to_global(file) + off;
+      cap = (uint32_t)size;
+      if (p[size] == 1) {                                  // LGS_SNAPPY_COMPRESSION
+        uint32_t want = 0, at = 0;
+        const uint64_t most = 32 * size + 64;
+        cap = varint32(p, &at, (uint32_t)size, &want) ? want : 0u;
+        if (cap > most) cap = (uint32_t)most;
+        if (cap > kMaxRoom) cap = kMaxRoom;
+      }
+    }
+    const uint32_t r16 = (cap + 15u) & ~15u;
+    out_cap[j] = cap;
+    room[j] = r16;
+    atomicAdd((unsigned long long*)&s_sum, (unsigned long long)r16);
+    atomicMax(&s_max, cap);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (s_sum) atomicAdd((unsigned long long*)&info[1], (unsigned long long)s_sum);
+    if (s_max) atomicMax((unsigned long long*)&info[2], (unsigned long long)s_max);
+    if (s_err) atomicOr((unsigned long long*)&info[3], 1ull);
+  }
+}
+
+// Every query's answer for a table that did not open.
+__global__ __launch_bounds__(256) void get_fail_kernel(uint32_t nq, uint32_t st,
+                                                       uint8_t* __restrict__ called,
+                                                       uint8_t* __restrict__ status,
+                                                       uint8_t* __restrict__ verdict,
+                                                       uint64_t* __restrict__ out_key_off,
+                                                       uint64_t* __restrict__ out_val_off) {
+  const uint32_t q = blockIdx.x * 256 + threadIdx.x;
+  if (q > nq) return;
+  out_key_off[q] = 0;
+  out_val_off[q] = 0;
+  if (q == nq) return;
+  called[q] = 0;
+  status[q] = (uint8_t)st;
+  if (verdict) verdict[q] = kGetNotFound;
+}
+
+// The room's cap stands for "corrupted compressed block contents"
+// (format.c:247-251).
+__global__ __launch_bounds__(256) void nospace_is_corrupt_kernel(uint8_t* __restrict__ status,
+                                                                 uint32_t nq) {
+  const uint32_t q = blockIdx.x * 256 + threadIdx.x;
+  if (q < nq && status[q] == kStNoSpace) status[q] = (uint8_t)kStCorrupt;
+}
+
 }  // namespace
+
+hipError_t launch_live_mark(const uint8_t* state, const uint8_t* match, const uint8_t* seek_status,
+                            const uint32_t* entry_pos, uint32_t nq, uint32_t index_len,
+                            uint8_t* pre, uint32_t* qblock, uint32_t* mark, hipStream_t s) {
+  if (nq == 0) return hipSuccess;
+  hipLaunchKernelGGL(live_mark_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, state, match,
+                     seek_status, entry_pos, nq, index_len, pre, qblock, mark);
+  return hipGetLastError();
+}
+
+hipError_t launch_qblock(const uint64_t* rank, const uint64_t* hoff, const uint64_t* hsize,
+                         uint32_t nq, uint32_t* qblock, uint64_t* b_off, uint64_t* b_size,
+                         hipStream_t s) {
+  if (nq == 0) return hipSuccess;
+  hipLaunchKernelGGL(qblock_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, rank, hoff, hsize, nq,
+                     qblock, b_off, b_size);
+  return hipGetLastError();
+}
+
+hipError_t launch_block_plan(const uint8_t* file, uint64_t file_len, const uint64_t* b_off,
+                             const uint64_t* b_size, uint32_t bound, uint32_t* out_cap,
+                             uint32_t* room, uint64_t* info, hipStream_t s) {
+  if (bound == 0) return hipSuccess;
+  hipLaunchKernelGGL(block_plan_kernel, dim3((bound + 255) / 256), dim3(256), 0, s, file, file_len,
+                     b_off, b_size, bound, out_cap, room, info);
+  return hipGetLastError();
+}
+
+hipError_t launch_get_fail(uint32_t nq, uint8_t st, uint8_t* called, uint8_t* status,
+                           uint8_t* verdict, uint64_t* out_key_off, uint64_t* out_val_off,
+                           hipStream_t s) {
+  hipLaunchKernelGGL(get_fail_kernel, dim3((nq + 256) / 256), dim3(256), 0, s, nq, (uint32_t)st,
+                     called, status, verdict, out_key_off, out_val_off);
+  return hipGetLastError();
+}
+
+hipError_t launch_nospace_is_corrupt(uint8_t* status, uint32_t nq, hipStream_t s) {
+  if (nq == 0) return hipSuccess;
+  hipLaunchKernelGGL(nospace_is_corrupt_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, status, nq);
+  return hipGetLastError();
+}
 
 hipError_t launch_block_seek(const SeekArgs& a, hipStream_t s) {
   if (a.nq == 0) return hipSuccess;

@@ -19,6 +19,9 @@ the batched C ABI that does both for many blocks per launch
   (src/table/block.c:324-451);
 * ``get_host``        -- ``ldb_table_internal_get`` for many keys against one
   table image (src/table/table.c:314-364);
+* ``open_table``      -- ``ldb_table_open`` once: the decoded index and filter
+  blocks (and, if asked, the image) stay on the device, and ``.get`` /
+  ``.get_dev`` are ``ldb_table_internal_get`` against them;
 * ``index_host``      -- ``ldb_table_open``'s footer, index-block handles and
   metaindex filter handle (src/table/table.c:78-180), the handles the batched
   read takes.
@@ -42,7 +45,7 @@ _L = _native.lib()
 
 __all__ = [
     "crc32c_batch", "write_blocks", "read_blocks", "write_blocks_host", "read_blocks_host",
-    "index_host", "FILTER_NAME", "seek_blocks_host", "get_host", "build_blocks", "build_blocks_host", "build_table_host",
+    "index_host", "FILTER_NAME", "seek_blocks_host", "get_host", "open_table", "OpenTable", "build_blocks", "build_blocks_host", "build_table_host",
     "LGS_NO_COMPRESSION", "LGS_SNAPPY_COMPRESSION", "LGS_TRAILER_SIZE", "LGS_ST_OK",
     "LGS_ST_CORRUPT", "LGS_ST_NOSPACE", "LGS_ST_IOERR", "LGS_ST_BADCRC", "LGS_ST_BADTYPE",
     "LGS_GET_NOTFOUND", "LGS_GET_FOUND", "LGS_GET_DELETED", "LGS_GET_CORRUPT",
@@ -442,3 +445,141 @@ def get_host(file, keys: Sequence[bytes], verify: bool = True, paranoid_checks: 
         a, b, c = int(okoff[q]), int(ovoff[q]), int(okoff[q + 1])
         res.append((out[a:b].tobytes(), out[b:c].tobytes()))
     return res, status[:nq], verdict[:nq]
+
+
+class OpenTable:
+    """A table opened once (lgs_table_open_host): the decoded index and filter
+    blocks stay on the device, and every ``get`` runs against them.  With
+    ``resident`` the whole image does, and ``get_dev`` serves keys and results
+    in device memory.  Also a context manager; ``close`` is idempotent."""
+
+    def __init__(self, file, paranoid_checks: bool = False, internal_keys: bool = False,
+                 filter_name: str | None = FILTER_NAME, resident: bool = False):
+        import ctypes as C
+        # A borrowed image must outlive the handle: a numpy array is kept as it
+        # is (the caller's buffer), anything else is copied once.
+        if isinstance(file, np.ndarray) and file.dtype == np.uint8 and file.flags.c_contiguous:
+            img = file
+        else:
+            img = np.frombuffer(bytes(file), dtype=np.uint8)
+        self._len = len(img)
+        self._img = img if len(img) else np.zeros(1, dtype=np.uint8)
+        self.internal_keys = bool(internal_keys)
+        self.resident = bool(resident)
+        h, st = C.c_void_p(None), C.c_uint8(0)
+        check(_L.lgs_table_open_host(self._img.ctypes.data, self._len,
+                                     1 if paranoid_checks else 0, 1 if internal_keys else 0,
+                                     filter_name.encode() if filter_name else None,
+                                     1 if resident else 0, C.byref(h), C.byref(st)),
+              "lgs_table_open_host")
+        self._h = h
+        self.status = st.value
+        if resident:
+            self._img = None                  # the call has uploaded it
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None and h.value:
+            _L.lgs_table_close(h)
+        self._img = None
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the table is closed")
+        return self._h
+
+    def info(self) -> dict:
+        """lgs_table_info: status, resident, index_bytes, filter_bytes, device_bytes."""
+        import ctypes as C
+        st, res = C.c_uint8(0), C.c_int(0)
+        ib, fb, db = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        check(_L.lgs_table_info(self._handle(), C.byref(st), C.byref(res), C.byref(ib),
+                                C.byref(fb), C.byref(db)), "lgs_table_info")
+        return {"status": st.value, "resident": bool(res.value), "index_bytes": ib.value,
+                "filter_bytes": fb.value, "device_bytes": db.value}
+
+    def get(self, keys: Sequence[bytes], verify: bool = True, out_cap: Optional[int] = None):
+        """ldb_table_internal_get for every key (lgs_table_get): what get_host
+        returns, ([(key, value) or None], status, verdict)."""
+        import ctypes as C
+        nq = len(keys)
+        kbuf, koff, klen = _pack_keys(list(keys))
+        called = np.zeros(max(nq, 1), dtype=np.uint8)
+        status = np.zeros(max(nq, 1), dtype=np.uint8)
+        verdict = np.zeros(max(nq, 1), dtype=np.uint8)
+        okoff = np.zeros(nq + 1, dtype=np.uint64)
+        ovoff = np.zeros(nq + 1, dtype=np.uint64)
+        need = C.c_size_t(0)
+        cap = int(out_cap) if out_cap is not None else max(4096, 128 * nq)
+        for attempt in range(2):
+            out = np.empty(max(cap, 1), dtype=np.uint8)
+            rc = _L.lgs_table_get(self._handle(), 1 if verify else 0, kbuf.ctypes.data,
+                                  koff.ctypes.data, klen.ctypes.data, nq, called.ctypes.data,
+                                  status.ctypes.data, verdict.ctypes.data, out.ctypes.data, cap,
+                                  okoff.ctypes.data, ovoff.ctypes.data, C.byref(need))
+            if rc != LGS_ENOSPC or attempt:
+                break
+            cap = need.value                   # one retry with the size it asked for
+        check(rc, "lgs_table_get")
+        res = []
+        for q in range(nq):
+            if not called[q]:
+                res.append(None)
+                continue
+            a, b, c = int(okoff[q]), int(ovoff[q]), int(okoff[q + 1])
+            res.append((out[a:b].tobytes(), out[b:c].tobytes()))
+        return res, status[:nq], verdict[:nq]
+
+    def get_dev(self, d_keys, d_key_off, d_key_len, verify: bool = True,
+                out_cap: Optional[int] = None, stream=None):
+        """lgs_table_get_dev on torch device tensors (uint8 keys readable 16
+        bytes past their end, int64 offsets, int32 lengths; resident tables
+        only).  Returns a dict of device tensors ``called``, ``status``,
+        ``verdict`` (uint8, nq), ``out`` (uint8), ``out_key_off`` and
+        ``out_val_off`` (int64, nq + 1), and the int ``out_needed``; complete
+        on the stream when it returns.  One retry on LGS_ENOSPC, as ``get``."""
+        import ctypes as C
+        torch = _torch()
+        nq = int(d_key_len.numel())
+        dev = d_keys.device
+        u8 = lambda n: torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)   # noqa: E731
+        called, status, verdict = u8(nq), u8(nq), u8(nq)
+        okoff = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+        ovoff = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+        need = C.c_size_t(0)
+        cap = int(out_cap) if out_cap is not None else max(4096, 128 * nq)
+        sp = _stream_ptr(stream)
+        for attempt in range(2):
+            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            rc = _L.lgs_table_get_dev(self._handle(), 1 if verify else 0, d_keys.data_ptr(),
+                                      d_key_off.data_ptr(), d_key_len.data_ptr(), nq,
+                                      called.data_ptr(), status.data_ptr(), verdict.data_ptr(),
+                                      out.data_ptr(), cap, okoff.data_ptr(), ovoff.data_ptr(),
+                                      C.byref(need), sp)
+            if rc != LGS_ENOSPC or attempt:
+                break
+            cap = need.value
+        check(rc, "lgs_table_get_dev")
+        return {"called": called[:nq], "status": status[:nq], "verdict": verdict[:nq], "out": out,
+                "out_key_off": okoff, "out_val_off": ovoff, "out_needed": need.value}
+
+
+def open_table(file, paranoid_checks: bool = False, internal_keys: bool = False,
+               filter_name: str | None = FILTER_NAME, resident: bool = False) -> OpenTable:
+    """ldb_table_open once (lgs_table_open_host).  With ``resident=False`` the
+    image is borrowed: pass a numpy uint8 array and keep it unchanged in its
+    data blocks while the table is open (bytes are copied once instead)."""
+    return OpenTable(file, paranoid_checks, internal_keys, filter_name, resident)

@@ -16,8 +16,13 @@ blocks of 4 KiB).
   different machine: no reference binary runs here) and passed in with
   --ref-json; reported beside ours with that caveat.
 
+* --open: the opened-table legs instead (lgs_table_open_host, lgs_table_get,
+  lgs_table_get_dev, and lgs_table_get_host and the index block's
+  lgs_table_read_host re-measured beside them), to
+  profiles/table_get_open.json.
+
 Writes one JSON object to --out (default profiles/table_get.json) and prints
-it.  usage: python tools/bench_table_get.py [--entries N] [--queries Q]
+it.  usage: python tools/bench_table_get.py [--entries N] [--queries Q] [--open]
 """
 from __future__ import annotations
 
@@ -33,8 +38,160 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
+def open_legs(a, L, check, e, np, torch) -> dict:
+    """The opened-table legs (--open) on the same table image and key sets:
+    lgs_table_open_host (borrowed and resident), lgs_table_get and
+    lgs_table_get_dev for 1 024 and --queries keys, and beside them, in the
+    same run, lgs_table_get_host and lgs_table_read_host of the index block
+    alone.  Host calls by wall clock, lgs_table_get_dev by HIP events; median,
+    minimum and maximum of --iters runs after two warm-ups."""
+    from bench_table_build import host_build
+    n, nq, bs = a.entries, a.queries, a.block_size
+    keys = e[0]
+    rng = np.random.default_rng(20240611)
+    pick = rng.integers(0, n, size=nq)
+    qkeys = np.concatenate([keys[:24 * n].reshape(n, 24)[pick].reshape(-1),
+                            np.zeros(16, dtype=np.uint8)])
+    qoff = np.arange(nq, dtype=np.uint64) * 24
+    qlen = np.full(nq, 24, dtype=np.uint32)
+    _, img = host_build(L, check, e, n, bs)
+    img = np.concatenate([img, np.zeros(1, dtype=np.uint8)])
+    flen = len(img) - 1
+    small = min(1024, nq)
+    out = {"workload": f"fillseq, {n} entries of 24 + 100 bytes, block_size {bs}; "
+                       f"{nq} uniformly drawn stored keys", "entries": n, "queries": nq,
+           "file_size": flen, "iters": a.iters}
+    good = True
+
+    def stats(ts):
+        return {"median_ms": float(np.median(ts)) * 1e3, "min_ms": min(ts) * 1e3,
+                "max_ms": max(ts) * 1e3}
+
+    def wall(fn, after=None):
+        ts = []
+        for k in range(a.iters + 2):
+            t0 = time.perf_counter()
+            r = fn()
+            t1 = time.perf_counter()
+            if after:
+                after(r)
+            if k >= 2:
+                ts.append(t1 - t0)
+        return stats(ts)
+
+    class Res:
+        def __init__(self, m):
+            self.called = np.zeros(m, dtype=np.uint8)
+            self.status = np.zeros(m, dtype=np.uint8)
+            self.verdict = np.zeros(m, dtype=np.uint8)
+            self.cap = 124 * m
+            self.out = np.empty(self.cap, dtype=np.uint8)
+            self.ko = np.zeros(m + 1, dtype=np.uint64)
+            self.vo = np.zeros(m + 1, dtype=np.uint64)
+            self.need = C.c_size_t(0)
+
+        def good(self):
+            return bool(self.called.all()) and bool((self.status == 1).all()) and \
+                bool((self.verdict == 1).all()) and self.need.value == self.cap
+
+    # ---- the unchanged path, re-measured ----
+    for m, name in ((nq, "get_host"), (small, "get_host_1024")):
+        r = Res(m)
+        out[name] = wall(lambda: check(L.lgs_table_get_host(
+            img.ctypes.data, flen, 1, 0, 1, None, qkeys.ctypes.data, qoff.ctypes.data,
+            qlen.ctypes.data, m, r.called.ctypes.data, r.status.ctypes.data, r.verdict.ctypes.data,
+            r.out.ctypes.data, r.cap, r.ko.ctypes.data, r.vo.ctypes.data, C.byref(r.need)),
+            "lgs_table_get_host"))
+        good &= r.good()
+    foot = img[flen - 48:flen].tobytes()
+    at, hs = 0, []
+    for _ in range(4):
+        v, sh = 0, 0
+        while True:
+            c = foot[at]
+            at += 1
+            v |= (c & 127) << sh
+            sh += 7
+            if c < 128:
+                break
+        hs.append(v)
+    hoff, hsize = np.array([hs[2]], dtype=np.uint64), np.array([hs[3]], dtype=np.uint64)
+    icap = np.array([16 << 20], dtype=np.uint32)
+    iout = np.empty(int(icap[0]) + 16, dtype=np.uint8)
+    ioo, iol, ist = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint32), np.zeros(1, dtype=np.uint8)
+    out["read_host_index_block"] = wall(lambda: check(L.lgs_table_read_host(
+        img.ctypes.data, flen, hoff.ctypes.data, hsize.ctypes.data, 1, 0, iout.ctypes.data,
+        ioo.ctypes.data, icap.ctypes.data, iol.ctypes.data, ist.ctypes.data), "lgs_table_read_host"))
+    good &= int(ist[0]) == 1
+    out["index_block_bytes"] = int(iol[0])
+    out["index_block_stored_bytes"] = int(hs[3])
+
+    # ---- open, get, get_dev ----
+    dq = torch.from_numpy(qkeys).cuda()
+    dqo = torch.from_numpy(qoff.view(np.int64)).cuda()
+    dql = torch.from_numpy(qlen.view(np.int32)).cuda()
+    for resident, mode in ((0, "borrowed"), (1, "resident")):
+        h, st = C.c_void_p(None), C.c_uint8(0)
+
+        def opn():
+            hh = C.c_void_p(None)
+            check(L.lgs_table_open_host(img.ctypes.data, flen, 0, 1, None, resident, C.byref(hh),
+                                        C.byref(st)), "lgs_table_open_host")
+            return hh
+
+        out[f"open_{mode}"] = wall(opn, after=L.lgs_table_close)
+        h = opn()
+        good &= st.value == 1
+        ib, db = C.c_uint64(0), C.c_uint64(0)
+        check(L.lgs_table_info(h, None, None, C.byref(ib), None, C.byref(db)), "lgs_table_info")
+        out[f"device_bytes_{mode}"] = db.value
+        good &= ib.value == out["index_block_bytes"]
+        for m, name in ((nq, "get"), (small, "get_1024")):
+            r = Res(m)
+            out[f"{name}_{mode}"] = wall(lambda: check(L.lgs_table_get(
+                h, 1, qkeys.ctypes.data, qoff.ctypes.data, qlen.ctypes.data, m, r.called.ctypes.data,
+                r.status.ctypes.data, r.verdict.ctypes.data, r.out.ctypes.data, r.cap,
+                r.ko.ctypes.data, r.vo.ctypes.data, C.byref(r.need)), "lgs_table_get"))
+            good &= r.good()
+        if resident:
+            for m, name in ((nq, "get_dev"), (small, "get_dev_1024")):
+                u8 = lambda k: torch.zeros(k, dtype=torch.uint8, device="cuda")   # noqa: E731
+                called, status, verdict, res = u8(m), u8(m), u8(m), u8(124 * m)
+                ko = torch.zeros(m + 1, dtype=torch.int64, device="cuda")
+                vo = torch.zeros(m + 1, dtype=torch.int64, device="cuda")
+                need = C.c_size_t(0)
+                sp = torch.cuda.current_stream().cuda_stream
+                ts = []
+                for k in range(a.iters + 2):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    check(L.lgs_table_get_dev(h, 1, dq.data_ptr(), dqo.data_ptr(), dql.data_ptr(), m,
+                                              called.data_ptr(), status.data_ptr(), verdict.data_ptr(),
+                                              res.data_ptr(), 124 * m, ko.data_ptr(), vo.data_ptr(),
+                                              C.byref(need), sp), "lgs_table_get_dev")
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if k >= 2:
+                        ts.append(e0.elapsed_time(e1) / 1e3)
+                out[name] = stats(ts)
+                good &= bool(called.all()) and bool((status == 1).all()) and \
+                    bool((verdict == 1).all()) and need.value == 124 * m
+        L.lgs_table_close(h)
+    out["all_found"] = bool(good)
+    # What the design predicts (DESIGN §4.6), as this run has it.
+    out["get_1024_under_index_block_read"] = {
+        mode: out[f"get_1024_{mode}"]["median_ms"] < out["read_host_index_block"]["median_ms"]
+        for mode in ("borrowed", "resident")}
+    out["get_not_slower_than_get_host"] = {
+        mode: out[f"get_{mode}"]["median_ms"] <= out["get_host"]["max_ms"]
+        for mode in ("borrowed", "resident")}
+    return out
+
+
 def main() -> None:
     p = argparse.ArgumentParser()
+    p.add_argument("--open", action="store_true",
+                   help="the opened-table legs only, to profiles/table_get_open.json")
     p.add_argument("--entries", type=int, default=65536 * 36)
     p.add_argument("--queries", type=int, default=1 << 20)
     p.add_argument("--block-size", type=int, default=4096)
@@ -56,6 +213,18 @@ def main() -> None:
     n, nq, bs = a.entries, a.queries, a.block_size
     e = fillseq_entries(n)
     keys = e[0]
+    if a.open:
+        out = open_legs(a, L, check, e, np, torch)
+        path = a.out if a.out != p.get_default("out") else \
+            os.path.join(ROOT, "profiles", "table_get_open.json")
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1, sort_keys=True)
+            f.write("\n")
+        print(json.dumps(out))
+        if not out["all_found"]:
+            sys.exit(1)
+        return
     out = {"workload": f"fillseq, {n} entries of 24 + 100 bytes, block_size {bs}; "
                        f"{nq} uniformly drawn stored keys", "entries": n, "queries": nq}
 

@@ -317,6 +317,60 @@ class Table:
         return True, ST_OK, e[1], block[e[2]:e[2] + e[3]]
 
 
+NO_BLOCK = 0xFFFFFFFF
+
+
+def index_lookup(t: Table, key: bytes):
+    """ldb_table_internal_get up to the block read, as the device steps have
+    it: (state, seek status, entry offset, handle, live).  state 0: the index
+    seek found no entry; 1: an entry whose value is a handle; 2: one whose
+    value is none.  live: the query goes on to read a block (a handle, and no
+    filter or a filter match)."""
+    import oracle
+    ist, e = block_seek(t.index, key, t.internal)
+    if e is None:
+        return 0, ist, None, None, False
+    h = handle_import(t.index[e[2]:e[2] + e[3]])
+    if h is None:
+        return 2, ist, e[0], None, False
+    live = t.filter is None or oracle.bloom_restatement().filter_matches(
+        t.filter, h[0], key, t.internal)
+    return 1, ist, e[0], h, live
+
+
+def number_blocks(t: Table, keys):
+    """The distinct blocks of a batch as lgs_table_get numbers them
+    (live_mark_kernel, the scan of the marks, qblock_kernel): returns
+    (pre, qblock, nb, handles).
+
+    pre[q] is the status of a query that reads no block.  A live query marks
+    the index entry it found, in an array as long as the index block: the key
+    is the entry's offset, not the (offset, size) it carries, so two entries
+    with one handle are two blocks.  The exclusive scan of the marks is each
+    marked entry's rank, in file order whatever the order of the queries;
+    qblock[q] is its entry's rank or NO_BLOCK, nb the number of marks, and
+    handles[b] the handle of block b."""
+    nq = len(keys)
+    if t.index is None:
+        return [t.status] * nq, [NO_BLOCK] * nq, 0, []
+    marks = [0] * len(t.index)
+    pre, pos, handle_at = [], [], {}
+    for k in keys:
+        state, ist, at, h, live = index_lookup(t, k)
+        pre.append(ist if state == 0 else (ST_CORRUPT if state == 2 else ST_OK))
+        pos.append(at if live else None)
+        if live:
+            marks[at] = 1
+            handle_at[at] = h
+    rank, acc = [], 0
+    for m in marks:
+        rank.append(acc)
+        acc += m
+    qblock = [NO_BLOCK if p is None else rank[p] for p in pos]
+    handles = [handle_at[at] for at in sorted(handle_at)]
+    return pre, qblock, acc, handles
+
+
 def main() -> None:
     import os
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
