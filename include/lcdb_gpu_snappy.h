@@ -484,7 +484,7 @@ int lgs_table_get_host(const uint8_t *file, uint64_t file_len, int verify_checks
  *
  * lgs_table_info: any output may be NULL.  *index_bytes / *filter_bytes: the
  * decoded blocks' lengths (0: none); *device_bytes: the memory the handle
- * holds on the device.
+ * holds on the device (from its first scan on, the index entry list too).
  *
  * lgs_table_get: lgs_table_get_host's contract, word for word, minus the open
  * arguments.  Between the index seek and the block read it differs inside:
@@ -524,6 +524,131 @@ int lgs_table_get_dev(lgs_table *table, int verify_checksums, const uint8_t *d_k
                       uint8_t *d_called, uint8_t *d_status, uint8_t *d_verdict,
                       uint8_t *d_out, size_t out_cap, uint64_t *d_out_key_off,
                       uint64_t *d_out_val_off, size_t *out_needed, void *stream);
+
+/* ---- forward scans ----
+ *
+ * The table iterator's forward half: ldb_tableiter_create, then first or
+ * seek, then next until invalid.  Blocks in, the entries out flat as (keys,
+ * key_off, key_len, vals, val_off, val_len): the layout lgs_block_cut_dev,
+ * lgs_block_emit_dev and lgs_table_build_host take, so build(scan(table)) is
+ * the table again.
+ *
+ * A forward scan of one block is ldb_blockiter_first + ldb_blockiter_next
+ * until invalid (block.c:247-296, 411-415).  A block under 4 bytes or with a
+ * restart count that does not fit is an error iterator (LGS_ST_CORRUPT, no
+ * entries); one with 0 restarts is empty (LGS_ST_OK).  Otherwise the walk
+ * begins at restart[0], clamped to the restart array's offset, and parses
+ * entry after entry up to that offset; it ends LGS_ST_CORRUPT at the first
+ * entry that does not decode, whose `shared` exceeds the previous key's
+ * length, or (internal_keys) whose key has under 8 bytes, the entries before
+ * it delivered.  The restart array plays no other part, and keys are
+ * delivered as parsed: their order is not checked.
+ *
+ * Blocks: d_blocks, d_block_off, d_block_len and the optional d_block_status
+ * as for lgs_block_seek_dev; block_bytes: at least the sum of d_block_len
+ * (under 3 * 2^31).  d_walk_from / d_emit_from (NULL, or 0xffffffff for a
+ * block: not given): the offset in block b where its walk begins instead of
+ * restart[0], and the first offset whose entry is delivered -- how a scan
+ * follows a seek, which goes on parsing from the restart run it chose.
+ *
+ * Two device calls, because the host needs the totals between them to size
+ * the outputs.  lgs_block_entries_count_dev writes d_entry_first (nblocks + 1:
+ * each block's first entry number, the total last), d_status (nblocks) and
+ * d_counts[4] = {entries, key bytes, value bytes, longest key}.
+ * lgs_block_entries_emit_dev, given n = d_counts[0], rebuilds every key in
+ * full and writes d_keys (d_counts[1] + 16 bytes), d_key_off (n + 1), d_key_len
+ * (n), d_vals (d_counts[2] + 16), d_val_off (n + 1), d_val_len (n): the 16
+ * bytes meet the builder's "readable 16 bytes past the end".  Both take the
+ * same lgs_block_entries_scratch(nblocks, block_bytes) bytes of device
+ * scratch (12 + 8 bytes per possible entry, a third of block_bytes), left
+ * alone between them, and both are asynchronous on `stream`.  nblocks = 0 and
+ * blocks without entries are fine.  The work is linear in the block bytes
+ * plus the bytes delivered, whatever the blocks hold.
+ *
+ * lgs_block_entries_host: host arrays in and out (a pooled context, one
+ * synchronisation between the two calls, scratch sized by the entries found).
+ * entry_first and status are always written, needed[3] = {entries, key bytes,
+ * value bytes}; LGS_ENOSPC when entry_cap, key_cap or val_cap is smaller, and
+ * then no entry is written. */
+size_t lgs_block_entries_scratch(uint32_t nblocks, uint64_t block_bytes);
+int lgs_block_entries_count_dev(const uint8_t *d_blocks, const uint64_t *d_block_off,
+                                const uint32_t *d_block_len, const uint8_t *d_block_status,
+                                uint32_t nblocks, uint64_t block_bytes,
+                                const uint32_t *d_walk_from, const uint32_t *d_emit_from,
+                                int internal_keys, uint32_t *d_entry_first, uint8_t *d_status,
+                                uint64_t *d_counts, void *d_scratch, size_t scratch_bytes,
+                                void *stream);
+int lgs_block_entries_emit_dev(const uint8_t *d_blocks, const uint64_t *d_block_off,
+                               const uint32_t *d_block_len, const uint8_t *d_block_status,
+                               uint32_t nblocks, uint64_t block_bytes,
+                               const uint32_t *d_walk_from, const uint32_t *d_emit_from,
+                               int internal_keys, uint32_t n, uint8_t *d_keys,
+                               uint64_t *d_key_off, uint32_t *d_key_len, uint8_t *d_vals,
+                               uint64_t *d_val_off, uint32_t *d_val_len, void *d_scratch,
+                               size_t scratch_bytes, void *stream);
+int lgs_block_entries_host(const uint8_t *blocks, const uint64_t *block_off,
+                           const uint32_t *block_len, const uint8_t *block_status,
+                           uint32_t nblocks, const uint32_t *walk_from, const uint32_t *emit_from,
+                           int internal_keys, uint32_t *entry_first, uint8_t *status,
+                           uint8_t *keys, size_t key_cap, uint64_t *key_off, uint32_t *key_len,
+                           uint8_t *vals, size_t val_cap, uint64_t *val_off, uint32_t *val_len,
+                           uint32_t entry_cap, uint64_t *needed);
+
+/* A forward scan of an opened table: two_level_iterator.c over the block
+ * scan, with table.c:229-300 as the block function.  The index block's
+ * entries are walked as above; each value goes through ldb_handle_import
+ * (LGS_ST_CORRUPT for that block when it is no handle), then the block is read
+ * (a failure is that read's status).  A block that yields an error, or ends
+ * in one, is skipped and the scan goes on (ldb_twoiter_skip_forward); the
+ * scan's final status is the index walk's own when that is not LGS_ST_OK,
+ * else the first block status in index order that is not (ldb_twoiter_saverr
+ * keeps the first).
+ *
+ * One call delivers a window of index entries [b0, b0 + max_blocks): b0 =
+ * first_block, or with has_start the block ldb_twoiter_seek's index seek
+ * names for start[0 .. start_len), where a fresh data iterator then seeks;
+ * the window's first block is walked from the restart run that seek chose
+ * and delivered from the entry it found (nothing, and the seek's status, when
+ * it found none), every later block from its first entry.  Results: the entry
+ * arrays above; block_entry_first (max_blocks + 1) and block_status
+ * (max_blocks) per block of the window; *blocks_done; *next_block, the
+ * first_block of the next call; *at_end; *index_status, the index walk's
+ * status, meaningful once *at_end.  needed[4] = {entries, key bytes, value
+ * bytes, blocks}: LGS_ENOSPC when a capacity is smaller (no entry is written;
+ * enlarge the buffers or shrink the window).  needed[3] is set only for a seek
+ * into a damaged index block that finds an entry the walk from restart[0]
+ * does not visit: the entries from there to where the two walks meet are one
+ * window, whatever max_blocks says.  A table that did not open has no
+ * iterator: no blocks, *at_end, *index_status = its status.
+ *
+ * The first scan of a handle builds its index entry list (positions, decoded
+ * handles, the walk's end status) once, under std::call_once, from the
+ * handle's pool; lgs_table_info counts it in *device_bytes from then on.  Any
+ * number of threads may scan one handle at once.  Read-backs per call: the
+ * window's room (a resident image; a borrowed one is planned on the host),
+ * then the counts; with has_start the index seek's entry first.  No call
+ * synchronises the whole device.
+ *
+ * lgs_table_scan_dev: every array in device memory, queued on `stream` (which
+ * the call synchronises itself for the read-backs) and complete on it when
+ * the call returns; key_cap and val_cap include the 16 spare bytes and needed
+ * reports them, so the results are lgs_block_cut_dev's input as they stand.
+ * start and the scalar results stay host words.  Resident tables only:
+ * LGS_EINVAL otherwise. */
+int lgs_table_scan(lgs_table *table, int verify_checksums, const uint8_t *start,
+                   uint32_t start_len, int has_start, uint32_t first_block, uint32_t max_blocks,
+                   uint8_t *keys, size_t key_cap, uint64_t *key_off, uint32_t *key_len,
+                   uint8_t *vals, size_t val_cap, uint64_t *val_off, uint32_t *val_len,
+                   uint32_t entry_cap, uint32_t *block_entry_first, uint8_t *block_status,
+                   uint32_t *blocks_done, uint32_t *next_block, int *at_end,
+                   uint8_t *index_status, uint64_t *needed);
+int lgs_table_scan_dev(lgs_table *table, int verify_checksums, const uint8_t *start,
+                       uint32_t start_len, int has_start, uint32_t first_block,
+                       uint32_t max_blocks, uint8_t *d_keys, size_t key_cap, uint64_t *d_key_off,
+                       uint32_t *d_key_len, uint8_t *d_vals, size_t val_cap, uint64_t *d_val_off,
+                       uint32_t *d_val_len, uint32_t entry_cap, uint32_t *d_block_entry_first,
+                       uint8_t *d_block_status, uint32_t *blocks_done, uint32_t *next_block,
+                       int *at_end, uint8_t *index_status, uint64_t *needed, void *stream);
 
 /* Devices and diagnostics. */
 /* The drop-in's current footprint: pinned and device bytes held by its

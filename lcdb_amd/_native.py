@@ -94,6 +94,24 @@ _SIGS = {
                                 C.c_size_t, _vp, _vp, C.POINTER(C.c_size_t)]),
     "lgs_table_get_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp,
                                     C.c_size_t, _vp, _vp, C.POINTER(C.c_size_t), _vp]),
+    "lgs_block_entries_scratch": (C.c_size_t, [C.c_uint32, C.c_uint64]),
+    "lgs_block_entries_count_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp,
+                                              C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "lgs_block_entries_emit_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp,
+                                             C.c_int, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             C.c_size_t, _vp]),
+    "lgs_block_entries_host": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_int, _vp,
+                                         _vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp, _vp,
+                                         C.c_uint32, _vp]),
+    "lgs_table_scan": (C.c_int, [_vp, C.c_int, _vp, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
+                                 _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_uint32,
+                                 _vp, _vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                 C.POINTER(C.c_int), C.POINTER(C.c_uint8), _vp]),
+    "lgs_table_scan_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
+                                     _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp, _vp,
+                                     C.c_uint32, _vp, _vp, C.POINTER(C.c_uint32),
+                                     C.POINTER(C.c_uint32), C.POINTER(C.c_int),
+                                     C.POINTER(C.c_uint8), _vp, _vp]),
     "lgs_dropin_footprint": (C.c_int, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                        C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]),
     "lgs_service_quiesce": (C.c_int, []),

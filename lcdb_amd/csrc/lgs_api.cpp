@@ -31,6 +31,7 @@
 #include <string.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -46,6 +47,7 @@
 
 #include "lgs_block.h"
 #include "lgs_launch.h"
+#include "lgs_scan.h"
 #include "lgs_seek.h"
 #include "lgs_table_tail.h"
 
@@ -3084,6 +3086,21 @@ struct lgs_table {
   uint8_t* d = nullptr;
   size_t d_bytes = 0;
   size_t o_filter = 0, o_olen = 0, o_bst = 0, o_zero = 0, o_img = 0;   // the index block at 0
+  // The index entry list, built once by the first scan and
+  // read-only from then on: the index block's entries in walk order, on the
+  // device (hoff | hsize | state) and on the host, and the walk's end status.
+  std::once_flag list_once;
+  int list_rc = LGS_OK;
+  char list_err[256] = {0};
+  std::unique_ptr<Scratch> list_mem;
+  uint8_t* list_d = nullptr;
+  std::atomic<size_t> list_bytes{0};
+  size_t l_hsize = 0, l_state = 0;                 // hoff at 0
+  uint32_t list_n = 0;
+  uint8_t list_status = LGS_ST_OK;
+  std::vector<uint32_t> list_pos;
+  std::vector<uint64_t> list_hoff, list_hsize;
+  std::vector<uint8_t> list_state;
 };
 
 namespace {
@@ -3405,10 +3422,13 @@ void table_free(lgs_table* t) {
   int cur = -1;
   const bool moved = hipGetDevice(&cur) == hipSuccess && cur != t->device &&
                      hipSetDevice(t->device) == hipSuccess;
+  if (t->list_mem) (void)t->list_mem->release();
   (void)t->mem->release();                 // stream-ordered, then that stream alone is waited on
   (void)hipStreamSynchronize(t->stream);
   t->mem.reset();
+  t->list_mem.reset();
   t->d = nullptr;
+  t->list_d = nullptr;
   if (moved) (void)hipSetDevice(cur);
 }
 
@@ -3528,7 +3548,7 @@ int lgs_table_info(const lgs_table* table, uint8_t* status, int* resident, uint6
   if (resident) *resident = table->resident;
   if (index_bytes) *index_bytes = table->index_len;
   if (filter_bytes) *filter_bytes = table->filter_bytes;
-  if (device_bytes) *device_bytes = table->mem ? table->d_bytes : 0;
+  if (device_bytes) *device_bytes = table->mem ? table->d_bytes + table->list_bytes.load() : 0;
   return LGS_OK;
 }
 
@@ -3549,6 +3569,732 @@ int lgs_table_get_dev(lgs_table* table, int verify_checksums, const uint8_t* d_k
   const GetIo io{true, d_keys, d_key_off, d_key_len, d_called, d_status, d_verdict, d_out, out_cap,
                  d_out_key_off, d_out_val_off, out_needed};
   return table_get(table, verify_checksums, io, nq, (hipStream_t)stream);
+}
+
+// ---- forward scans: the entries of blocks and of opened tables ----
+
+namespace {
+
+// The scan's device scratch (EntriesScratch, lgs_scan.h) in two parts: what
+// the count leaves per block, and what the emit writes per entry (W walked,
+// N delivered).
+struct EntriesBlockLayout {
+  size_t head, wcnt, dcnt, wfirst, dfirst, part, total;
+  explicit EntriesBlockLayout(uint32_t nb) {
+    Layout L;
+    head = L.take(16);
+    wcnt = L.take(4 * (size_t)nb);
+    dcnt = L.take(4 * (size_t)nb);
+    wfirst = L.take(8 * ((size_t)nb + 1));
+    dfirst = L.take(8 * ((size_t)nb + 1));
+    part = L.take(8 * scan_parts(nb) + 8);
+    total = L.at;
+  }
+};
+struct EntriesEntryLayout {
+  size_t src, shared, link, eblk, emeta, part, total;
+  EntriesEntryLayout(uint64_t W, uint64_t N) {
+    Layout L;
+    src = L.take(4 * (size_t)W);
+    shared = L.take(4 * (size_t)W);
+    link = L.take(4 * (size_t)W);
+    eblk = L.take(4 * (size_t)N);
+    emeta = L.take(4 * (size_t)N);
+    part = L.take(8 * scan_parts((uint32_t)N) + 8);
+    total = L.at;
+  }
+};
+
+EntriesScratch entries_scratch(uint8_t* pb, const EntriesBlockLayout& B, uint8_t* pe,
+                               const EntriesEntryLayout* E) {
+  EntriesScratch w{(uint64_t*)(pb + B.head), (uint32_t*)(pb + B.wcnt), (uint32_t*)(pb + B.dcnt),
+                   (uint64_t*)(pb + B.wfirst), (uint64_t*)(pb + B.dfirst), (uint64_t*)(pb + B.part),
+                   nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (E) {
+    w.part = (uint64_t*)(pe + E->part);
+    w.src = (uint32_t*)(pe + E->src);
+    w.shared = (uint32_t*)(pe + E->shared);
+    w.link = (uint32_t*)(pe + E->link);
+    w.eblk = (uint32_t*)(pe + E->eblk);
+    w.emeta = (uint32_t*)(pe + E->emeta);
+  }
+  return w;
+}
+
+// A block holds at most a third of its bytes in entries.
+int entries_bound(uint64_t block_bytes, uint64_t* cap) {
+  *cap = block_bytes / 3 + 1;
+  if (*cap > kMaxEntries)
+    return fail(LGS_EINVAL, "%llu block bytes: under 3 * 2^31 supported",
+                (unsigned long long)block_bytes);
+  return LGS_OK;
+}
+
+}  // namespace
+
+size_t lgs_block_entries_scratch(uint32_t nblocks, uint64_t block_bytes) {
+  uint64_t cap = 0;
+  if (entries_bound(block_bytes, &cap) != LGS_OK) return 0;
+  return EntriesBlockLayout(nblocks).total + EntriesEntryLayout(cap, cap).total;
+}
+
+int lgs_block_entries_count_dev(const uint8_t* d_blocks, const uint64_t* d_block_off,
+                                const uint32_t* d_block_len, const uint8_t* d_block_status,
+                                uint32_t nblocks, uint64_t block_bytes, const uint32_t* d_walk_from,
+                                const uint32_t* d_emit_from, int internal_keys,
+                                uint32_t* d_entry_first, uint8_t* d_status, uint64_t* d_counts,
+                                void* d_scratch, size_t scratch_bytes, void* stream) {
+  if (internal_keys != 0 && internal_keys != 1)
+    return fail(LGS_EINVAL, "internal_keys must be 0 or 1");
+  if (nblocks > kMaxEntries) return fail(LGS_EINVAL, "%u blocks: under 2^31 supported", nblocks);
+  if (!d_entry_first || !d_counts || !d_scratch ||
+      (nblocks && (!d_blocks || !d_block_off || !d_block_len || !d_status)))
+    return fail(LGS_EINVAL, "NULL argument");
+  uint64_t cap = 0;
+  LGS_TRY(entries_bound(block_bytes, &cap));
+  const EntriesBlockLayout B(nblocks);
+  if (scratch_bytes < B.total + EntriesEntryLayout(cap, cap).total)
+    return fail(LGS_EINVAL, "scratch %zu < %zu (lgs_block_entries_scratch)", scratch_bytes,
+                B.total + EntriesEntryLayout(cap, cap).total);
+  const EntriesIn in{d_blocks, d_block_off, d_block_len, d_block_status, nblocks, d_walk_from,
+                     d_emit_from, (uint32_t)internal_keys};
+  LGS_HIP(launch_entries_count(in, entries_scratch((uint8_t*)d_scratch, B, nullptr, nullptr),
+                               d_entry_first, d_status, d_counts, (hipStream_t)stream));
+  return LGS_OK;
+}
+
+int lgs_block_entries_emit_dev(const uint8_t* d_blocks, const uint64_t* d_block_off,
+                               const uint32_t* d_block_len, const uint8_t* d_block_status,
+                               uint32_t nblocks, uint64_t block_bytes, const uint32_t* d_walk_from,
+                               const uint32_t* d_emit_from, int internal_keys, uint32_t n,
+                               uint8_t* d_keys, uint64_t* d_key_off, uint32_t* d_key_len,
+                               uint8_t* d_vals, uint64_t* d_val_off, uint32_t* d_val_len,
+                               void* d_scratch, size_t scratch_bytes, void* stream) {
+  if (internal_keys != 0 && internal_keys != 1)
+    return fail(LGS_EINVAL, "internal_keys must be 0 or 1");
+  if (nblocks > kMaxEntries) return fail(LGS_EINVAL, "%u blocks: under 2^31 supported", nblocks);
+  if (!d_key_off || !d_val_off || !d_scratch ||
+      (n && (!d_blocks || !d_block_off || !d_block_len || !d_keys || !d_key_len || !d_vals ||
+             !d_val_len)))
+    return fail(LGS_EINVAL, "NULL argument");
+  uint64_t cap = 0;
+  LGS_TRY(entries_bound(block_bytes, &cap));
+  if (n > cap) return fail(LGS_EINVAL, "%u entries in %llu block bytes", n,
+                           (unsigned long long)block_bytes);
+  const EntriesBlockLayout B(nblocks);
+  const EntriesEntryLayout E(cap, cap);
+  if (scratch_bytes < B.total + E.total)
+    return fail(LGS_EINVAL, "scratch %zu < %zu (lgs_block_entries_scratch)", scratch_bytes,
+                B.total + E.total);
+  const EntriesIn in{d_blocks, d_block_off, d_block_len, d_block_status, nblocks, d_walk_from,
+                     d_emit_from, (uint32_t)internal_keys};
+  uint8_t* p = (uint8_t*)d_scratch;
+  LGS_HIP(launch_entries_emit(in, entries_scratch(p, B, p + B.total, &E), cap, n, d_keys, d_key_off,
+                              d_key_len, d_vals, d_val_off, d_val_len, (hipStream_t)stream));
+  return LGS_OK;
+}
+
+int lgs_block_entries_host(const uint8_t* blocks, const uint64_t* block_off,
+                           const uint32_t* block_len, const uint8_t* block_status, uint32_t nblocks,
+                           const uint32_t* walk_from, const uint32_t* emit_from, int internal_keys,
+                           uint32_t* entry_first, uint8_t* status, uint8_t* keys, size_t key_cap,
+                           uint64_t* key_off, uint32_t* key_len, uint8_t* vals, size_t val_cap,
+                           uint64_t* val_off, uint32_t* val_len, uint32_t entry_cap,
+                           uint64_t* needed) {
+  if (internal_keys != 0 && internal_keys != 1)
+    return fail(LGS_EINVAL, "internal_keys must be 0 or 1");
+  if (nblocks > kMaxEntries) return fail(LGS_EINVAL, "%u blocks: under 2^31 supported", nblocks);
+  if (!entry_first || !key_off || !val_off || !needed ||
+      (nblocks && (!blocks || !block_off || !block_len || !status)))
+    return fail(LGS_EINVAL, "NULL argument");
+  needed[0] = needed[1] = needed[2] = 0;
+  entry_first[0] = 0;
+  key_off[0] = val_off[0] = 0;
+  if (nblocks == 0) return LGS_OK;
+  size_t bb = 0;
+  for (uint32_t b = 0; b < nblocks; ++b) bb += block_len[b];
+  uint64_t cap = 0;
+  LGS_TRY(entries_bound(bb, &cap));
+  Lease lease(batch_pool());
+  LGS_TRY(lease.acquire());
+  Ctx& c = lease.ctx();
+  hipStream_t s = c.stream;
+  const EntriesBlockLayout B(nblocks);
+  Layout L;  // uploads | downloads | device-only
+  const size_t o_blk = L.take(bb + 16);
+  const size_t o_boff = L.take(8 * (size_t)nblocks);
+  const size_t o_blen = L.take(4 * (size_t)nblocks);
+  const size_t o_bst = L.take(nblocks);
+  const size_t o_wf = L.take(4 * (size_t)nblocks);
+  const size_t o_ef = L.take(4 * (size_t)nblocks);
+  const size_t up_end = L.at;
+  const size_t o_cnt = L.take(8 * kEntryCounts);      // downloads
+  const size_t o_head = L.take(16);
+  const size_t o_first = L.take(4 * ((size_t)nblocks + 1));
+  const size_t o_st = L.take(nblocks);
+  const size_t pin_end = L.at;
+  const size_t o_scr = L.take(B.total);
+  LGS_TRY(ctx_reserve(c, L.at, pin_end));
+  uint8_t* h = c.h_buf;
+  uint8_t* d = c.d_buf;
+  {
+    uint64_t* boff = (uint64_t*)(h + o_boff);
+    size_t at = 0;
+    for (uint32_t b = 0; b < nblocks; ++b) {
+      boff[b] = at;
+      at += block_len[b];
+    }
+    memcpy(h + o_blen, block_len, 4 * (size_t)nblocks);
+    par_for(nblocks, bb, [&](uint32_t b0, uint32_t b1) {
+      for (uint32_t b = b0; b < b1; ++b) memcpy(h + o_blk + boff[b], blocks + block_off[b], block_len[b]);
+    });
+    memset(h + o_blk + bb, 0, 16);
+    if (block_status) memcpy(h + o_bst, block_status, nblocks);
+    if (walk_from) memcpy(h + o_wf, walk_from, 4 * (size_t)nblocks);
+    if (emit_from) memcpy(h + o_ef, emit_from, 4 * (size_t)nblocks);
+  }
+  LGS_HIP(hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, s));
+  const EntriesIn in{d + o_blk, (const uint64_t*)(d + o_boff), (const uint32_t*)(d + o_blen),
+                     block_status ? d + o_bst : nullptr, nblocks,
+                     walk_from ? (const uint32_t*)(d + o_wf) : nullptr,
+                     emit_from ? (const uint32_t*)(d + o_ef) : nullptr, (uint32_t)internal_keys};
+  const EntriesScratch w0 = entries_scratch(d + o_scr, B, nullptr, nullptr);
+  uint64_t* d_cnt = (uint64_t*)(d + o_cnt);
+  LGS_HIP(launch_entries_count(in, w0, (uint32_t*)(d + o_first), d + o_st, d_cnt, s));
+  LGS_HIP(hipMemcpyAsync(d + o_head, w0.head, 16, hipMemcpyDeviceToDevice, s));
+  LGS_HIP(hipMemcpyAsync(h + o_cnt, d + o_cnt, pin_end - o_cnt, hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipStreamSynchronize(s));   // the one read-back that sizes the outputs
+  const uint64_t* cnt = (const uint64_t*)(h + o_cnt);
+  const uint64_t walked = *(const uint64_t*)(h + o_head);
+  const uint64_t n = cnt[0], kb = cnt[1], vb = cnt[2];
+  memcpy(entry_first, h + o_first, 4 * ((size_t)nblocks + 1));
+  memcpy(status, h + o_st, nblocks);
+  needed[0] = n;
+  needed[1] = kb;
+  needed[2] = vb;
+  if (walked > cap || n > walked)
+    return fail(LGS_EINTERNAL, "%llu entries walked, %llu delivered in %zu block bytes",
+                (unsigned long long)walked, (unsigned long long)n, bb);
+  if (n > entry_cap || kb > key_cap || vb > val_cap)
+    return fail(LGS_ENOSPC, "%llu entries (entry_cap %u), keys %llu bytes (key_cap %zu), values %llu (val_cap %zu)",
+                (unsigned long long)n, entry_cap, (unsigned long long)kb, key_cap,
+                (unsigned long long)vb, val_cap);
+  if (n == 0) return LGS_OK;
+  const EntriesEntryLayout E(walked, n);
+  Layout O;  // downloads | device-only
+  const size_t q_keys = O.take((size_t)kb + 16);
+  const size_t q_vals = O.take((size_t)vb + 16);
+  const size_t q_koff = O.take(8 * ((size_t)n + 1));
+  const size_t q_voff = O.take(8 * ((size_t)n + 1));
+  const size_t q_klen = O.take(4 * (size_t)n);
+  const size_t q_vlen = O.take(4 * (size_t)n);
+  const size_t q_end = O.at;
+  const size_t q_scr = O.take(E.total);
+  Scratch arena(O.at, s);
+  if (arena.status() != hipSuccess)
+    return fail(LGS_ENOMEM, "%zu bytes of device memory for %llu entries: %s", O.at,
+                (unsigned long long)n, hipGetErrorString(arena.status()));
+  uint8_t* e = (uint8_t*)arena.get();
+  LGS_HIP(launch_entries_emit(in, entries_scratch(d + o_scr, B, e + q_scr, &E), walked, (uint32_t)n,
+                              e + q_keys, (uint64_t*)(e + q_koff), (uint32_t*)(e + q_klen),
+                              e + q_vals, (uint64_t*)(e + q_voff), (uint32_t*)(e + q_vlen), s));
+  LGS_TRY(ctx_reserve(c, 0, q_end));
+  h = c.h_buf;
+  LGS_HIP(hipMemcpyAsync(h, e, q_end, hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipStreamSynchronize(s));
+  memcpy(keys, h + q_keys, (size_t)kb);
+  memcpy(vals, h + q_vals, (size_t)vb);
+  memcpy(key_off, h + q_koff, 8 * ((size_t)n + 1));
+  memcpy(val_off, h + q_voff, 8 * ((size_t)n + 1));
+  memcpy(key_len, h + q_klen, 4 * (size_t)n);
+  memcpy(val_len, h + q_vlen, 4 * (size_t)n);
+  return LGS_OK;
+}
+
+namespace {
+
+// The index entry arrays of launch_index_slots / launch_index_walk inside one
+// allocation of `cap` entries.
+struct IndexListLayout {
+  size_t hoff, hsize, state, pos, info, total;
+  explicit IndexListLayout(size_t cap) {
+    Layout L;
+    hoff = L.take(8 * cap);
+    hsize = L.take(8 * cap);
+    state = L.take(cap);
+    pos = L.take(4 * cap);
+    info = L.take(32);
+    total = L.at;
+  }
+  IndexList at(uint8_t* p) const {
+    return IndexList{(uint32_t*)(p + pos), (uint64_t*)(p + hoff), (uint64_t*)(p + hsize), p + state,
+                     (uint64_t*)(p + info)};
+  }
+};
+
+// Builds the handle's index entry list on stream s (std::call_once's body).
+int index_list_build(lgs_table* t, Ctx& c, hipStream_t s) {
+  const size_t cap = (size_t)t->index_len / 3 + 1;
+  const IndexListLayout T(cap);
+  LGS_TRY(ctx_reserve(c, 0, T.total + 64));
+  uint8_t* h = c.h_buf;
+  Scratch tmp(T.total, s);
+  if (tmp.status() != hipSuccess)
+    return fail(LGS_ENOMEM, "%zu bytes of device memory for the index entries", T.total);
+  uint8_t* d = (uint8_t*)tmp.get();
+  const IndexList out = T.at(d);
+  const uint64_t* info = (const uint64_t*)(h + T.info);
+  LGS_HIP(launch_index_slots(t->d, t->index_len, (uint32_t)t->internal, (uint32_t)cap, out, s));
+  LGS_HIP(hipMemcpyAsync(h + T.info, d + T.info, 32, hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipStreamSynchronize(s));
+  if (info[2]) {
+    // The slots disagree: the single-lane walk, exact for any contents.
+    LGS_HIP(launch_index_walk(t->d, t->index_len, (uint32_t)t->internal, kNoOffset, (uint32_t)cap,
+                              out, s));
+    LGS_HIP(hipMemcpyAsync(h + T.info, d + T.info, 32, hipMemcpyDeviceToHost, s));
+    LGS_HIP(hipStreamSynchronize(s));
+  }
+  if (info[0] > cap) return fail(LGS_EINTERNAL, "%llu index entries in %u bytes",
+                                 (unsigned long long)info[0], t->index_len);
+  const uint32_t n = (uint32_t)info[0];
+  const uint8_t st = (uint8_t)info[1];
+  Layout F;
+  F.take(8 * (size_t)n);
+  const size_t l_hsize = F.take(8 * (size_t)n);
+  const size_t l_state = F.take((size_t)n + 16);
+  // From the handle's pool, on its stream; that stream alone is waited on
+  // before the copy on s.
+  t->list_mem.reset(new Scratch(F.at, t->stream));
+  if (t->list_mem->status() != hipSuccess) {
+    t->list_mem.reset();
+    return fail(LGS_ENOMEM, "%zu bytes of device memory for the index entries", F.at);
+  }
+  LGS_HIP(hipStreamSynchronize(t->stream));
+  uint8_t* ld = (uint8_t*)t->list_mem->get();
+  if (n) {
+    LGS_HIP(hipMemcpyAsync(ld, d + T.hoff, 8 * (size_t)n, hipMemcpyDeviceToDevice, s));
+    LGS_HIP(hipMemcpyAsync(ld + l_hsize, d + T.hsize, 8 * (size_t)n, hipMemcpyDeviceToDevice, s));
+    LGS_HIP(hipMemcpyAsync(ld + l_state, d + T.state, n, hipMemcpyDeviceToDevice, s));
+    LGS_HIP(hipMemcpyAsync(h + T.hoff, d + T.hoff, 8 * (size_t)n, hipMemcpyDeviceToHost, s));
+    LGS_HIP(hipMemcpyAsync(h + T.hsize, d + T.hsize, 8 * (size_t)n, hipMemcpyDeviceToHost, s));
+    LGS_HIP(hipMemcpyAsync(h + T.state, d + T.state, n, hipMemcpyDeviceToHost, s));
+    LGS_HIP(hipMemcpyAsync(h + T.pos, d + T.pos, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
+    LGS_HIP(hipStreamSynchronize(s));
+    const uint64_t* ho = (const uint64_t*)(h + T.hoff);
+    const uint64_t* hs = (const uint64_t*)(h + T.hsize);
+    const uint32_t* po = (const uint32_t*)(h + T.pos);
+    t->list_hoff.assign(ho, ho + n);
+    t->list_hsize.assign(hs, hs + n);
+    t->list_state.assign(h + T.state, h + T.state + n);
+    t->list_pos.assign(po, po + n);
+  }
+  t->list_d = ld;
+  t->l_hsize = l_hsize;
+  t->l_state = l_state;
+  t->list_n = n;
+  t->list_status = st;
+  t->list_bytes.store(F.at);
+  return LGS_OK;
+}
+
+int index_list(lgs_table* t, Ctx& c, hipStream_t s) {
+  std::call_once(t->list_once, [&] {
+    t->list_rc = index_list_build(t, c, s);
+    if (t->list_rc != LGS_OK) snprintf(t->list_err, sizeof t->list_err, "%s", t_err);
+  });
+  if (t->list_rc != LGS_OK) return fail(t->list_rc, "%s", t->list_err);
+  return LGS_OK;
+}
+
+// Where a scan's start comes from and where its results go: host memory
+// (lgs_table_scan) or device memory (lgs_table_scan_dev; the start key and
+// the scalar results stay host words).
+struct ScanIo {
+  bool dev;
+  const uint8_t* start; uint32_t start_len; int has_start;
+  uint32_t first_block, max_blocks;
+  uint8_t* keys; size_t key_cap; uint64_t* key_off; uint32_t* key_len;
+  uint8_t* vals; size_t val_cap; uint64_t* val_off; uint32_t* val_len; uint32_t entry_cap;
+  uint32_t* block_entry_first; uint8_t* block_status;
+  uint32_t* blocks_done; uint32_t* next_block; int* at_end; uint8_t* index_status;
+  uint64_t* needed;
+};
+
+int table_scan(lgs_table* t, int verify_checksums, const ScanIo& io, hipStream_t user_stream) {
+  if (!t || !io.blocks_done || !io.next_block || !io.at_end || !io.index_status || !io.needed ||
+      !io.key_off || !io.val_off || !io.block_entry_first)
+    return fail(LGS_EINVAL, "NULL argument");
+  if (io.has_start && !io.start && io.start_len) return fail(LGS_EINVAL, "NULL argument");
+  if (io.max_blocks == 0 || io.max_blocks > kMaxEntries)
+    return fail(LGS_EINVAL, "max_blocks must be at least 1 and under 2^31");
+  if (io.dev && !t->resident)
+    return fail(LGS_EINVAL, "lgs_table_scan_dev needs a table opened with resident = 1");
+  int dev = -1;
+  LGS_TRY(call_device(&dev));
+  if (dev != t->device)
+    return fail(LGS_EINVAL, "table opened on device %d, call on device %d", t->device, dev);
+  *io.blocks_done = 0;
+  *io.next_block = io.first_block;
+  *io.at_end = 1;
+  *io.index_status = t->status;
+  io.needed[0] = io.needed[1] = io.needed[2] = io.needed[3] = 0;
+  const size_t slack = io.dev ? 16 : 0;
+  auto no_entries = [&]() -> int {
+    if (io.dev) {
+      LGS_HIP(hipMemsetAsync(io.key_off, 0, 8, user_stream));
+      LGS_HIP(hipMemsetAsync(io.val_off, 0, 8, user_stream));
+      LGS_HIP(hipMemsetAsync(io.block_entry_first, 0, 4, user_stream));
+    } else {
+      io.key_off[0] = io.val_off[0] = 0;
+      io.block_entry_first[0] = 0;
+    }
+    return LGS_OK;
+  };
+  if (t->status != LGS_ST_OK) return no_entries();   // a table that did not open: no iterator
+  Lease lease(batch_pool());
+  LGS_TRY(lease.acquire());
+  Ctx& c = lease.ctx();
+  hipStream_t s = io.dev ? user_stream : c.stream;
+  const uint32_t internal_keys = (uint32_t)t->internal;
+  LGS_TRY(index_list(t, c, s));
+  *io.index_status = t->list_status;
+
+  // -- A: the window of index entries.  With a start key, ldb_twoiter_seek's
+  // index seek names its first entry.
+  const uint64_t* w_hoff = t->list_hoff.data();       // the window's entries on the host ...
+  const uint64_t* w_hsize = t->list_hsize.data();
+  const uint8_t* w_state = t->list_state.data();
+  const uint8_t* dl = t->list_d;                      // ... and on the device
+  const uint64_t* dw_hoff = (const uint64_t*)dl;
+  const uint64_t* dw_hsize = (const uint64_t*)(dl + t->l_hsize);
+  const uint8_t* dw_state = dl + t->l_state;
+  uint32_t b0 = io.first_block, nb = 0, next = 0;
+  bool at_end = true;
+  std::unique_ptr<Scratch> seek_mem, side_mem;
+  std::vector<uint64_t> side_hoff, side_hsize;
+  std::vector<uint8_t> side_state;
+  const uint8_t* d_start = nullptr;                   // the start key on the device
+  const uint64_t* d_start_off = nullptr;
+  const uint32_t* d_start_len = nullptr;
+  uint8_t* sk = nullptr;                              // the seeks' outputs
+  Layout S;
+  const size_t s_key = S.take((size_t)io.start_len + 16);
+  const size_t s_koff = S.take(8);
+  const size_t s_klen = S.take(4);
+  const size_t s_up = S.at;
+  const size_t s_epos = S.take(4);
+  const size_t s_sst = S.take(4);
+  const size_t s_down = S.at;
+  const size_t s_fkl = S.take(4);
+  const size_t s_vpos = S.take(4);
+  const size_t s_vlen = S.take(4);
+  const size_t s_rpos = S.take(lgs_block_seek_scratch(1));
+  if (io.has_start) {
+    LGS_TRY(ctx_reserve(c, 0, s_down + 64));
+    uint8_t* h = c.h_buf;
+    seek_mem.reset(new Scratch(S.at, s));
+    if (seek_mem->status() != hipSuccess)
+      return fail(LGS_ENOMEM, "%zu bytes of device memory for the seek", S.at);
+    sk = (uint8_t*)seek_mem->get();
+    memset(h, 0, s_up);
+    if (io.start_len) memcpy(h + s_key, io.start, io.start_len);
+    *(uint32_t*)(h + s_klen) = io.start_len;
+    LGS_HIP(hipMemcpyAsync(sk, h, s_up, hipMemcpyHostToDevice, s));
+    d_start = sk + s_key;
+    d_start_off = (const uint64_t*)(sk + s_koff);
+    d_start_len = (const uint32_t*)(sk + s_klen);
+    const SeekArgs ia{t->d, (const uint64_t*)(t->d + t->o_zero), (const uint32_t*)(t->d + t->o_olen),
+                      t->d + t->o_bst, 1, nullptr, d_start, d_start_off, d_start_len, 1,
+                      internal_keys, (uint32_t*)(sk + s_epos), (uint32_t*)(sk + s_fkl),
+                      (uint32_t*)(sk + s_vpos), (uint32_t*)(sk + s_vlen), sk + s_sst,
+                      (uint32_t*)(sk + s_rpos), nullptr, nullptr, nullptr};
+    LGS_HIP(launch_block_seek(ia, s));
+    LGS_HIP(hipMemcpyAsync(h + s_epos, sk + s_epos, s_down - s_epos, hipMemcpyDeviceToHost, s));
+    LGS_HIP(hipStreamSynchronize(s));
+    const uint32_t epos = *(const uint32_t*)(h + s_epos);
+    if (epos == kNoEntry) {
+      // An invalid index iterator: no block, and its status is the scan's.
+      *io.index_status = h[s_sst];
+      *io.next_block = t->list_n;
+      return no_entries();
+    }
+    const auto it = std::lower_bound(t->list_pos.begin(), t->list_pos.end(), epos);
+    if (it != t->list_pos.end() && *it == epos) {
+      b0 = (uint32_t)(it - t->list_pos.begin());
+    } else {
+      // The seek's entry is none the walk from restart[0] visits (a damaged
+      // index block): the entries from it up to where the two walks meet, by
+      // the serial walk, in one window.
+      const size_t cap = (size_t)t->index_len / 3 + 1;
+      const IndexListLayout T(cap);
+      LGS_TRY(ctx_reserve(c, 0, T.total + 64));
+      h = c.h_buf;
+      side_mem.reset(new Scratch(T.total, s));
+      if (side_mem->status() != hipSuccess)
+        return fail(LGS_ENOMEM, "%zu bytes of device memory for the index entries", T.total);
+      uint8_t* sd = (uint8_t*)side_mem->get();
+      LGS_HIP(launch_index_walk(t->d, t->index_len, internal_keys, epos, (uint32_t)cap, T.at(sd), s));
+      LGS_HIP(hipMemcpyAsync(h, sd, T.total, hipMemcpyDeviceToHost, s));
+      LGS_HIP(hipStreamSynchronize(s));
+      const uint64_t* info = (const uint64_t*)(h + T.info);
+      const uint32_t* po = (const uint32_t*)(h + T.pos);
+      uint32_t k = 0, join = t->list_n;
+      bool joined = false;
+      for (; k < info[0]; ++k) {
+        const auto j = std::lower_bound(t->list_pos.begin(), t->list_pos.end(), po[k]);
+        if (j != t->list_pos.end() && *j == po[k]) {
+          join = (uint32_t)(j - t->list_pos.begin());
+          joined = true;
+          break;
+        }
+      }
+      if (k > io.max_blocks) {
+        io.needed[3] = k;
+        return fail(LGS_ENOSPC, "the seek's window takes %u blocks, max_blocks %u", k, io.max_blocks);
+      }
+      const uint64_t* ho = (const uint64_t*)(h + T.hoff);
+      const uint64_t* hs = (const uint64_t*)(h + T.hsize);
+      side_hoff.assign(ho, ho + k);
+      side_hsize.assign(hs, hs + k);
+      side_state.assign(h + T.state, h + T.state + k);
+      w_hoff = side_hoff.data();
+      w_hsize = side_hsize.data();
+      w_state = side_state.data();
+      dw_hoff = (const uint64_t*)(sd + T.hoff);
+      dw_hsize = (const uint64_t*)(sd + T.hsize);
+      dw_state = sd + T.state;
+      b0 = 0;
+      nb = k;
+      next = join;
+      at_end = !joined;
+      if (!joined) *io.index_status = (uint8_t)info[1];
+    }
+  }
+  if (!side_mem) {
+    if (b0 > t->list_n) b0 = t->list_n;
+    nb = t->list_n - b0 < io.max_blocks ? t->list_n - b0 : io.max_blocks;
+    next = b0 + nb;
+    at_end = next >= t->list_n;
+    w_hoff += b0;
+    w_hsize += b0;
+    w_state += b0;
+    dw_hoff += b0;
+    dw_hsize += b0;
+    dw_state += b0;
+  }
+  *io.blocks_done = nb;
+  *io.next_block = next;
+  *io.at_end = at_end ? 1 : 0;
+  if (nb == 0) return no_entries();
+
+  // -- B: the window's blocks, read as a get reads its distinct blocks.
+  const EntriesBlockLayout EB(nb);
+  Layout P;  // resident: the plan, device-only
+  const size_t p_ocap = P.take(4 * (size_t)nb);
+  const size_t p_room = P.take(4 * (size_t)nb);
+  const size_t p_info = P.take(32);
+  size_t outb = 0, img = 0;
+  uint32_t max_cap = 0;
+  std::unique_ptr<Scratch> plan_mem;
+  std::vector<HandlePlan> plan;
+  uint8_t* pd = nullptr;
+  if (t->resident) {
+    LGS_TRY(ctx_reserve(c, 0, 64));
+    uint8_t* h = c.h_buf;
+    plan_mem.reset(new Scratch(P.at, s));
+    if (plan_mem->status() != hipSuccess)
+      return fail(LGS_ENOMEM, "%zu bytes of device memory for %u blocks", P.at, nb);
+    pd = (uint8_t*)plan_mem->get();
+    LGS_HIP(launch_plan_info((uint64_t*)(pd + p_info), nb, s));
+    LGS_HIP(launch_block_plan(t->d + t->o_img, t->file_len, dw_hoff, dw_hsize, nb,
+                              (uint32_t*)(pd + p_ocap), (uint32_t*)(pd + p_room),
+                              (uint64_t*)(pd + p_info), s));
+    LGS_HIP(hipMemcpyAsync(h, pd + p_info, 32, hipMemcpyDeviceToHost, s));
+    LGS_HIP(hipStreamSynchronize(s));   // the read-back that sizes the block read
+    const uint64_t* info = (const uint64_t*)h;
+    if (info[3]) return fail(LGS_EINVAL, "a block of 2^31 bytes or more: under 2^31 supported");
+    outb = (size_t)info[1];
+    max_cap = (uint32_t)info[2];
+  } else {
+    plan.resize(nb);
+    for (uint32_t j = 0; j < nb; ++j)
+      LGS_TRY(plan_handle(t->file, t->file_len, w_hoff[j], w_hsize[j], &plan[j]));
+    img = handles_image(w_hsize, plan.data(), nb, &outb, &max_cap);
+  }
+  const ReadScratch R(nb);
+  Layout B;  // uploads (a borrowed image only) | downloads | device-only
+  const size_t p_blk = B.take(t->resident ? 0 : img + 32);
+  const size_t p_hoff = B.take(8 * (size_t)nb);
+  const size_t p_hsize = B.take(8 * (size_t)nb);
+  const size_t p_ooff = B.take(8 * (size_t)nb);
+  const size_t p_ocap2 = B.take(4 * (size_t)nb);
+  const size_t p_state = B.take(nb);
+  const size_t pin_b = B.at;
+  const size_t p_cnt = B.take(8 * kEntryCounts);      // downloads
+  const size_t p_head = B.take(16);
+  const size_t p_first = B.take(4 * ((size_t)nb + 1));
+  const size_t p_st = B.take(nb);
+  const size_t down_end = B.at;
+  const size_t p_olen = B.take(4 * (size_t)nb);
+  const size_t p_bst = B.take(nb);
+  const size_t p_wf = B.take(4 * (size_t)nb);
+  const size_t p_ef = B.take(4 * (size_t)nb);
+  const size_t p_part = B.take(8 * scan_parts(nb) + 8);
+  const size_t p_rscr = B.take(R.total);
+  const size_t p_escr = B.take(EB.total);
+  const size_t p_out = B.take(outb + 16);
+  LGS_TRY(ctx_reserve(c, 0, std::max(pin_b, down_end - p_cnt) + 64));
+  uint8_t* h = c.h_buf;
+  Scratch arena(B.at, s);
+  if (arena.status() != hipSuccess)
+    return fail(LGS_ENOMEM, "%zu bytes of device memory for %u blocks: %s", B.at, nb,
+                hipGetErrorString(arena.status()));
+  uint8_t* e = (uint8_t*)arena.get();
+  const uint8_t* d_state = dw_state;
+  if (t->resident) {
+    LGS_HIP(launch_scan(2, nullptr, (const uint32_t*)(pd + p_room), (uint64_t*)(e + p_part), p_out,
+                        (uint64_t*)(e + p_ooff), nullptr, nb, s));
+    LGS_TRY(table_read(t->d + t->o_img, t->file_len, dw_hoff, dw_hsize, nb, verify_checksums, e,
+                       (const uint64_t*)(e + p_ooff), (const uint32_t*)(pd + p_ocap), max_cap,
+                       (uint32_t*)(e + p_olen), e + p_bst, e + p_rscr, R, s));
+  } else {
+    size_t outb_end = 0;
+    stage_handles(t->file, w_hoff, w_hsize, plan.data(), nb, h + p_blk, (uint64_t*)(h + p_hoff),
+                  (uint64_t*)(h + p_hsize), (uint64_t*)(h + p_ooff), (uint32_t*)(h + p_ocap2), p_out,
+                  &outb_end);
+    memcpy(h + p_state, w_state, nb);
+    LGS_HIP(hipMemcpyAsync(e, h, pin_b, hipMemcpyHostToDevice, s));
+    LGS_TRY(table_read(e + p_blk, img + 16, (const uint64_t*)(e + p_hoff),
+                       (const uint64_t*)(e + p_hsize), nb, verify_checksums, e,
+                       (const uint64_t*)(e + p_ooff), (const uint32_t*)(e + p_ocap2), max_cap,
+                       (uint32_t*)(e + p_olen), e + p_bst, e + p_rscr, R, s));
+    d_state = e + p_state;
+  }
+  LGS_HIP(launch_scan_status(d_state, e + p_bst, nb, s));
+  const uint32_t* d_wf = nullptr;
+  const uint32_t* d_ef = nullptr;
+  if (io.has_start) {
+    // ldb_twoiter_seek's data seek: a fresh iterator on the window's first
+    // block; the scan goes on from the entry it found, in the restart run it
+    // chose.
+    LGS_HIP(hipMemsetAsync(e + p_wf, 0xff, p_part - p_wf, s));
+    const SeekArgs da{e, (const uint64_t*)(e + p_ooff), (const uint32_t*)(e + p_olen), e + p_bst, nb,
+                      nullptr, d_start, d_start_off, d_start_len, 1, internal_keys,
+                      (uint32_t*)(sk + s_epos), (uint32_t*)(sk + s_fkl), (uint32_t*)(sk + s_vpos),
+                      (uint32_t*)(sk + s_vlen), sk + s_sst, (uint32_t*)(sk + s_rpos), nullptr,
+                      nullptr, nullptr};
+    LGS_HIP(launch_block_seek(da, s));
+    LGS_HIP(launch_scan_seek_apply((const uint32_t*)(sk + s_epos), (const uint32_t*)(sk + s_rpos),
+                                   sk + s_sst, (uint32_t*)(e + p_wf), (uint32_t*)(e + p_ef),
+                                   e + p_bst, s));
+    d_wf = (const uint32_t*)(e + p_wf);
+    d_ef = (const uint32_t*)(e + p_ef);
+  }
+
+  // -- C: the entries (§2's two calls around the read-back of the counts).
+  const EntriesIn in{e, (const uint64_t*)(e + p_ooff), (const uint32_t*)(e + p_olen), e + p_bst, nb,
+                     d_wf, d_ef, internal_keys};
+  const EntriesScratch w0 = entries_scratch(e + p_escr, EB, nullptr, nullptr);
+  uint32_t* d_first = io.dev ? io.block_entry_first : (uint32_t*)(e + p_first);
+  uint8_t* d_st = io.dev ? io.block_status : e + p_st;
+  LGS_HIP(launch_entries_count(in, w0, d_first, d_st, (uint64_t*)(e + p_cnt), s));
+  LGS_HIP(hipMemcpyAsync(e + p_head, w0.head, 16, hipMemcpyDeviceToDevice, s));
+  LGS_HIP(hipMemcpyAsync(h, e + p_cnt, (io.dev ? p_first : down_end) - p_cnt, hipMemcpyDeviceToHost,
+                         s));
+  LGS_HIP(hipStreamSynchronize(s));   // the read-back that sizes the outputs
+  const uint64_t* cnt = (const uint64_t*)h;
+  const uint64_t walked = *(const uint64_t*)(h + (p_head - p_cnt));
+  const uint64_t n = cnt[0], kb = cnt[1], vb = cnt[2];
+  if (!io.dev) {
+    memcpy(io.block_entry_first, h + (p_first - p_cnt), 4 * ((size_t)nb + 1));
+    if (io.block_status) memcpy(io.block_status, h + (p_st - p_cnt), nb);
+  }
+  io.needed[0] = n;
+  io.needed[1] = kb + slack;
+  io.needed[2] = vb + slack;
+  if (walked > kMaxEntries || n > walked)
+    return fail(LGS_EINVAL, "%llu entries in one window: under 2^31 supported",
+                (unsigned long long)walked);
+  if (n > io.entry_cap || kb + slack > io.key_cap || vb + slack > io.val_cap)
+    return fail(LGS_ENOSPC, "%llu entries (entry_cap %u), keys %llu bytes (key_cap %zu), values %llu (val_cap %zu)",
+                (unsigned long long)n, io.entry_cap, (unsigned long long)(kb + slack), io.key_cap,
+                (unsigned long long)(vb + slack), io.val_cap);
+  if (n == 0) {
+    if (io.dev) {
+      LGS_HIP(hipMemsetAsync(io.key_off, 0, 8, s));
+      LGS_HIP(hipMemsetAsync(io.val_off, 0, 8, s));
+    } else {
+      io.key_off[0] = io.val_off[0] = 0;
+    }
+    return LGS_OK;
+  }
+  if (!io.keys || !io.key_len || !io.vals || !io.val_len) return fail(LGS_EINVAL, "NULL argument");
+  const EntriesEntryLayout EE(walked, n);
+  Layout O;  // downloads (a host call only) | device-only
+  const size_t q_keys = O.take(io.dev ? 0 : (size_t)kb + 16);
+  const size_t q_vals = O.take(io.dev ? 0 : (size_t)vb + 16);
+  const size_t q_koff = O.take(io.dev ? 0 : 8 * ((size_t)n + 1));
+  const size_t q_voff = O.take(io.dev ? 0 : 8 * ((size_t)n + 1));
+  const size_t q_klen = O.take(io.dev ? 0 : 4 * (size_t)n);
+  const size_t q_vlen = O.take(io.dev ? 0 : 4 * (size_t)n);
+  const size_t q_end = O.at;
+  const size_t q_scr = O.take(EE.total);
+  Scratch second(O.at, s);
+  if (second.status() != hipSuccess)
+    return fail(LGS_ENOMEM, "%zu bytes of device memory for %llu entries: %s", O.at,
+                (unsigned long long)n, hipGetErrorString(second.status()));
+  uint8_t* g = (uint8_t*)second.get();
+  const EntriesScratch w1 = entries_scratch(e + p_escr, EB, g + q_scr, &EE);
+  if (io.dev) {
+    // The scratch is freed on the stream behind the work that uses it.
+    LGS_HIP(launch_entries_emit(in, w1, walked, (uint32_t)n, io.keys, io.key_off, io.key_len, io.vals,
+                                io.val_off, io.val_len, s));
+    return LGS_OK;
+  }
+  LGS_HIP(launch_entries_emit(in, w1, walked, (uint32_t)n, g + q_keys, (uint64_t*)(g + q_koff),
+                              (uint32_t*)(g + q_klen), g + q_vals, (uint64_t*)(g + q_voff),
+                              (uint32_t*)(g + q_vlen), s));
+  LGS_TRY(ctx_reserve(c, 0, q_end));
+  h = c.h_buf;
+  LGS_HIP(hipMemcpyAsync(h, g, q_end, hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipStreamSynchronize(s));
+  memcpy(io.keys, h + q_keys, (size_t)kb);
+  memcpy(io.vals, h + q_vals, (size_t)vb);
+  memcpy(io.key_off, h + q_koff, 8 * ((size_t)n + 1));
+  memcpy(io.val_off, h + q_voff, 8 * ((size_t)n + 1));
+  memcpy(io.key_len, h + q_klen, 4 * (size_t)n);
+  memcpy(io.val_len, h + q_vlen, 4 * (size_t)n);
+  return LGS_OK;
+}
+
+}  // namespace
+
+int lgs_table_scan(lgs_table* table, int verify_checksums, const uint8_t* start,
+                   uint32_t start_len, int has_start, uint32_t first_block, uint32_t max_blocks,
+                   uint8_t* keys, size_t key_cap, uint64_t* key_off, uint32_t* key_len,
+                   uint8_t* vals, size_t val_cap, uint64_t* val_off, uint32_t* val_len,
+                   uint32_t entry_cap, uint32_t* block_entry_first, uint8_t* block_status,
+                   uint32_t* blocks_done, uint32_t* next_block, int* at_end, uint8_t* index_status,
+                   uint64_t* needed) {
+  const ScanIo io{false, start, start_len, has_start, first_block, max_blocks, keys, key_cap,
+                  key_off, key_len, vals, val_cap, val_off, val_len, entry_cap, block_entry_first,
+                  block_status, blocks_done, next_block, at_end, index_status, needed};
+  return table_scan(table, verify_checksums, io, nullptr);
+}
+
+int lgs_table_scan_dev(lgs_table* table, int verify_checksums, const uint8_t* start,
+                       uint32_t start_len, int has_start, uint32_t first_block,
+                       uint32_t max_blocks, uint8_t* d_keys, size_t key_cap, uint64_t* d_key_off,
+                       uint32_t* d_key_len, uint8_t* d_vals, size_t val_cap, uint64_t* d_val_off,
+                       uint32_t* d_val_len, uint32_t entry_cap, uint32_t* d_block_entry_first,
+                       uint8_t* d_block_status, uint32_t* blocks_done, uint32_t* next_block,
+                       int* at_end, uint8_t* index_status, uint64_t* needed, void* stream) {
+  if (!d_block_status) return fail(LGS_EINVAL, "NULL argument");
+  const ScanIo io{true, start, start_len, has_start, first_block, max_blocks, d_keys, key_cap,
+                  d_key_off, d_key_len, d_vals, val_cap, d_val_off, d_val_len, entry_cap,
+                  d_block_entry_first, d_block_status, blocks_done, next_block, at_end,
+                  index_status, needed};
+  return table_scan(table, verify_checksums, io, (hipStream_t)stream);
 }
 
 int lgs_device_count(void) { return visible_devices(); }

@@ -22,6 +22,11 @@ the batched C ABI that does both for many blocks per launch
 * ``open_table``      -- ``ldb_table_open`` once: the decoded index and filter
   blocks (and, if asked, the image) stay on the device, and ``.get`` /
   ``.get_dev`` are ``ldb_table_internal_get`` against them;
+* ``block_entries`` / ``block_entries_host`` -- ``ldb_blockiter_first`` +
+  ``_next`` until invalid for many decoded blocks (src/table/block.c:247-296,
+  411-415): their entries in ``build_blocks``' input layout;
+* ``OpenTable.scan`` / ``.scan_dev`` -- ``ldb_tableiter_create``, first or
+  seek, next until invalid (src/table/two_level_iterator.c, table.c:229-311);
 * ``index_host``      -- ``ldb_table_open``'s footer, index-block handles and
   metaindex filter handle (src/table/table.c:78-180), the handles the batched
   read takes.
@@ -45,7 +50,7 @@ _L = _native.lib()
 
 __all__ = [
     "crc32c_batch", "write_blocks", "read_blocks", "write_blocks_host", "read_blocks_host",
-    "index_host", "FILTER_NAME", "seek_blocks_host", "get_host", "open_table", "OpenTable", "build_blocks", "build_blocks_host", "build_table_host",
+    "index_host", "FILTER_NAME", "seek_blocks_host", "block_entries", "block_entries_host", "ScanError", "get_host", "open_table", "OpenTable", "build_blocks", "build_blocks_host", "build_table_host",
     "LGS_NO_COMPRESSION", "LGS_SNAPPY_COMPRESSION", "LGS_TRAILER_SIZE", "LGS_ST_OK",
     "LGS_ST_CORRUPT", "LGS_ST_NOSPACE", "LGS_ST_IOERR", "LGS_ST_BADCRC", "LGS_ST_BADTYPE",
     "LGS_GET_NOTFOUND", "LGS_GET_FOUND", "LGS_GET_DELETED", "LGS_GET_CORRUPT",
@@ -184,6 +189,54 @@ def build_blocks(d_keys, d_key_off, d_key_len, d_vals, d_val_off, d_val_len,
             "nblocks": nb, "raw_total": raw_total, "max_len": max_len}
 
 
+def block_entries(d_blocks, d_block_off, d_block_len, block_bytes: int, d_block_status=None,
+                  d_walk_from=None, d_emit_from=None, internal_keys: bool = False, stream=None):
+    """The entries of n decoded blocks, in walk order (lgs_block_entries_count_dev
+    + one read-back of the counts + lgs_block_entries_emit_dev).
+
+    d_blocks uint8, d_block_off int64, d_block_len int32, the optional
+    d_block_status uint8 and d_walk_from / d_emit_from int32 (-1: not given);
+    block_bytes: at least the sum of the lengths.  Returns a dict of device
+    tensors ``keys``, ``vals`` (16 spare bytes each), ``key_off``, ``val_off``
+    (int64, n + 1), ``key_len``, ``val_len`` (int32, n) -- build_blocks' input
+    -- ``entry_first`` (int32, blocks + 1), ``status`` (uint8, blocks), and the
+    ints ``n``, ``key_bytes``, ``val_bytes``, ``max_key``."""
+    torch = _torch()
+    nb = int(d_block_len.numel())
+    dev = d_blocks.device
+    sp = _stream_ptr(stream)
+    scr = torch.empty(max(int(_L.lgs_block_entries_scratch(nb, int(block_bytes))), 1),
+                      dtype=torch.uint8, device=dev)
+    first = torch.zeros(nb + 1, dtype=torch.int32, device=dev)
+    status = torch.zeros(max(nb, 1), dtype=torch.uint8, device=dev)
+    counts = torch.zeros(4, dtype=torch.int64, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    head = (d_blocks.data_ptr(), d_block_off.data_ptr(), d_block_len.data_ptr(),
+            ptr(d_block_status), nb, int(block_bytes), ptr(d_walk_from), ptr(d_emit_from),
+            1 if internal_keys else 0)
+    check(_L.lgs_block_entries_count_dev(*head, first.data_ptr(), status.data_ptr(),
+                                         counts.data_ptr(), scr.data_ptr(), int(scr.numel()), sp),
+          "lgs_block_entries_count_dev")
+    if stream is not None:
+        stream.synchronize()
+    n, kb, vb, mk = (int(x) for x in counts.cpu())
+    keys = torch.zeros(kb + 16, dtype=torch.uint8, device=dev)
+    vals = torch.zeros(vb + 16, dtype=torch.uint8, device=dev)
+    key_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    val_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    key_len = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    val_len = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    check(_L.lgs_block_entries_emit_dev(*head, n, keys.data_ptr(), key_off.data_ptr(),
+                                        key_len.data_ptr(), vals.data_ptr(), val_off.data_ptr(),
+                                        val_len.data_ptr(), scr.data_ptr(), int(scr.numel()), sp),
+          "lgs_block_entries_emit_dev")
+    if stream is not None:
+        scr.record_stream(stream)
+    return {"keys": keys, "key_off": key_off, "key_len": key_len[:n], "vals": vals,
+            "val_off": val_off, "val_len": val_len[:n], "entry_first": first,
+            "status": status[:nb], "n": n, "key_bytes": kb, "val_bytes": vb, "max_key": mk}
+
+
 # ---------------------------------------------------------------------------
 # Host bytes.
 # ---------------------------------------------------------------------------
@@ -296,6 +349,65 @@ def read_blocks_host(file, handle_off, handle_size, caps, verify: bool = True):
     res = [out[int(o):int(o) + int(k)].tobytes() if s == LGS_ST_OK else None
            for o, k, s in zip(ooff, olen, st)]
     return res, st
+
+
+def _unpack_entries(keys, key_off, key_len, vals, val_off, val_len, n):
+    kb, vb = keys.tobytes(), vals.tobytes()
+    return [(kb[int(key_off[i]):int(key_off[i]) + int(key_len[i])],
+             vb[int(val_off[i]):int(val_off[i]) + int(val_len[i])]) for i in range(n)]
+
+
+def block_entries_host(blocks: Sequence[bytes], internal_keys: bool = False, block_status=None,
+                       walk_from=None, emit_from=None, caps=None):
+    """ldb_blockiter_first + _next until invalid for every decoded block
+    (lgs_block_entries_host).  Returns ([[(key, value)] per block], status
+    array).  walk_from / emit_from: per block an offset or None.  caps:
+    (entries, key bytes, value bytes) to call with; by default one call with
+    nothing sizes the outputs.  Too small raises ScanError with ``.needed``."""
+    nb = len(blocks)
+    blen = np.array([len(b) for b in blocks], dtype=np.uint32)
+    boff = np.zeros(nb, dtype=np.uint64)
+    if nb:
+        boff[1:] = np.cumsum(blen[:-1], dtype=np.uint64)
+    bbuf = np.frombuffer(b"".join(blocks) + b"\0" * 16, dtype=np.uint8)
+    bst = None if block_status is None else np.ascontiguousarray(block_status, dtype=np.uint8)
+
+    def offs(a):
+        if a is None:
+            return None
+        return np.array([0xFFFFFFFF if x is None else x for x in a], dtype=np.uint32)
+
+    wf, ef = offs(walk_from), offs(emit_from)
+    first = np.zeros(nb + 1, dtype=np.uint32)
+    status = np.zeros(max(nb, 1), dtype=np.uint8)
+    needed = np.zeros(3, dtype=np.uint64)
+    ptr = lambda a: a.ctypes.data if a is not None else None   # noqa: E731
+
+    def call(n, kb, vb):
+        keys = np.zeros(kb + 16, dtype=np.uint8)
+        vals = np.zeros(vb + 16, dtype=np.uint8)
+        koff = np.zeros(n + 1, dtype=np.uint64)
+        voff = np.zeros(n + 1, dtype=np.uint64)
+        klen = np.zeros(max(n, 1), dtype=np.uint32)
+        vlen = np.zeros(max(n, 1), dtype=np.uint32)
+        rc = _L.lgs_block_entries_host(bbuf.ctypes.data, boff.ctypes.data, blen.ctypes.data,
+                                       ptr(bst), nb, ptr(wf), ptr(ef), 1 if internal_keys else 0,
+                                       first.ctypes.data, status.ctypes.data, keys.ctypes.data, kb,
+                                       koff.ctypes.data, klen.ctypes.data, vals.ctypes.data, vb,
+                                       voff.ctypes.data, vlen.ctypes.data, n, needed.ctypes.data)
+        return rc, (keys, koff, klen, vals, voff, vlen)
+
+    rc, out = call(*(caps if caps is not None else (0, 0, 0)))
+    if rc == LGS_ENOSPC and caps is None:
+        rc, out = call(*(int(x) for x in needed))
+    if rc == LGS_ENOSPC:
+        e = ScanError("lgs_block_entries_host: outputs too small")
+        e.needed = tuple(int(x) for x in needed)
+        e.untouched = not (out[0].any() or out[3].any() or out[2].any() or out[5].any())
+        raise e
+    check(rc, "lgs_block_entries_host")
+    flat = _unpack_entries(*out, int(needed[0]))
+    return [flat[int(first[b]):int(first[b + 1])] for b in range(nb)], status[:nb]
 
 
 FILTER_NAME = "filter.leveldb.BuiltinBloomFilter2"   # "filter." + bloom.c's policy name
@@ -447,6 +559,11 @@ def get_host(file, keys: Sequence[bytes], verify: bool = True, paranoid_checks: 
     return res, status[:nq], verdict[:nq]
 
 
+class ScanError(_native.LgsError):
+    """A scan that ended in a status other than LGS_ST_OK (``.status``), or
+    outputs too small for lgs_block_entries_host (``.needed``)."""
+
+
 class OpenTable:
     """A table opened once (lgs_table_open_host): the decoded index and filter
     blocks stay on the device, and every ``get`` runs against them.  With
@@ -575,6 +692,124 @@ class OpenTable:
         check(rc, "lgs_table_get_dev")
         return {"called": called[:nq], "status": status[:nq], "verdict": verdict[:nq], "out": out,
                 "out_key_off": okoff, "out_val_off": ovoff, "out_needed": need.value}
+
+    # ---- forward scans (lgs_table_scan, lgs_table_scan_dev) ----
+
+    def _scan_call(self, fn, dev, verify, start, first_block, max_blocks, caps, stream=None):
+        """One window: (dict, raw arrays) with the capacities grown as the
+        call asks (LGS_ENOSPC reports the sizes; at most three calls)."""
+        import ctypes as C
+        torch = _torch() if dev is not None else None
+        n_cap, k_cap, v_cap = caps
+        sk = np.frombuffer((start or b"") + b"\0" * 16, dtype=np.uint8)
+        done, nxt, at_end = C.c_uint32(0), C.c_uint32(0), C.c_int(0)
+        ist = C.c_uint8(0)
+        needed = np.zeros(4, dtype=np.uint64)
+        for _ in range(4):
+            if dev is None:
+                mk = lambda n, dt: np.zeros(max(n, 1), dtype=dt)   # noqa: E731
+                ptr = lambda a: a.ctypes.data   # noqa: E731
+                t8, t32, t64 = np.uint8, np.uint32, np.uint64
+            else:
+                mk = lambda n, dt: torch.zeros(max(n, 1), dtype=dt, device=dev)   # noqa: E731
+                ptr = lambda a: a.data_ptr()   # noqa: E731
+                t8, t32, t64 = torch.uint8, torch.int32, torch.int64
+            keys, vals = mk(k_cap, t8), mk(v_cap, t8)
+            koff, voff = mk(n_cap + 1, t64), mk(n_cap + 1, t64)
+            klen, vlen = mk(n_cap, t32), mk(n_cap, t32)
+            first, bst = mk(max_blocks + 1, t32), mk(max_blocks, t8)
+            args = [self._handle(), 1 if verify else 0, sk.ctypes.data, len(start or b""),
+                    1 if start is not None else 0, int(first_block), int(max_blocks), ptr(keys),
+                    k_cap, ptr(koff), ptr(klen), ptr(vals), v_cap, ptr(voff), ptr(vlen), n_cap,
+                    ptr(first), ptr(bst), C.byref(done), C.byref(nxt), C.byref(at_end),
+                    C.byref(ist), needed.ctypes.data]
+            if dev is not None:
+                args.append(_stream_ptr(stream))
+            rc = fn(*args)
+            if rc != LGS_ENOSPC:
+                break
+            grow = lambda cap, need: cap if cap >= need else need + need // 8   # noqa: E731
+            n_cap = grow(n_cap, int(needed[0]))
+            k_cap = grow(k_cap, int(needed[1]))
+            v_cap = grow(v_cap, int(needed[2]))
+            max_blocks = max(max_blocks, int(needed[3]))
+        check(rc, "lgs_table_scan_dev" if dev is not None else "lgs_table_scan")
+        nb, n = done.value, int(needed[0])
+        return {"keys": keys, "key_off": koff[:n + 1], "key_len": klen[:n], "vals": vals,
+                "val_off": voff[:n + 1], "val_len": vlen[:n], "block_entry_first": first[:nb + 1],
+                "block_status": bst[:nb], "n": n, "key_bytes": int(needed[1]),
+                "val_bytes": int(needed[2]), "blocks_done": nb, "next_block": nxt.value,
+                "at_end": bool(at_end.value), "index_status": ist.value,
+                "caps": (n_cap, k_cap, v_cap)}
+
+    def scan_window(self, start: Optional[bytes] = None, first_block: int = 0,
+                    max_blocks: int = 1024, verify: bool = True, caps=(0, 0, 0)):
+        """One call of lgs_table_scan: the entries of index entries
+        [first_block, first_block + max_blocks) (with ``start``: from the
+        block its seek names).  Returns a dict: ``entries`` [(key, value)],
+        ``block_entry_first``, ``block_status``, ``blocks_done``,
+        ``next_block``, ``at_end``, ``index_status``, ``caps``."""
+        r = self._scan_call(_L.lgs_table_scan, None, verify, start, first_block, max_blocks, caps)
+        r["entries"] = _unpack_entries(r["keys"], r["key_off"], r["key_len"], r["vals"],
+                                       r["val_off"], r["val_len"], r["n"])
+        return r
+
+    def scan(self, start: Optional[bytes] = None, end: Optional[bytes] = None,
+             verify: bool = True, max_blocks: int = 1024):
+        """ldb_tableiter_create, first (or seek(start)), next until invalid: a
+        generator of (key, value), a window of ``max_blocks`` index entries a
+        call.  Stops before the first key with compare(key, end) >= 0 under
+        the table's comparator, in order across windows (a caller's ``while
+        valid && cmp(key, end) < 0``).  ``self.scan_status`` is the
+        iterator's status where the generator stopped; a status other than
+        LGS_ST_OK at the end raises ScanError after the last entry."""
+        import struct
+
+        def before_end(k: bytes) -> bool:
+            if end is None:
+                return True
+            if not self.internal_keys:
+                return k < end
+            if k[:-8] != end[:-8]:
+                return k[:-8] < end[:-8]
+            return struct.unpack("<Q", k[-8:])[0] > struct.unpack("<Q", end[-8:])[0]
+
+        self.scan_status = LGS_ST_OK
+        saved, nxt, first, caps = LGS_ST_OK, 0, True, (0, 0, 0)
+        while True:
+            r = self.scan_window(start if first else None, nxt, max_blocks, verify, caps)
+            first, caps, ef = False, r["caps"], r["block_entry_first"]
+            for j in range(r["blocks_done"]):
+                for k, v in r["entries"][int(ef[j]):int(ef[j + 1])]:
+                    if not before_end(k):
+                        self.scan_status = saved
+                        return
+                    yield k, v
+                if saved == LGS_ST_OK and int(r["block_status"][j]) != LGS_ST_OK:
+                    saved = int(r["block_status"][j])     # ldb_twoiter_saverr keeps the first
+            nxt = r["next_block"]
+            if r["at_end"]:
+                break
+        self.scan_status = r["index_status"] if r["index_status"] != LGS_ST_OK else saved
+        if self.scan_status != LGS_ST_OK:
+            e = ScanError(f"table scan ended with status {self.scan_status}")
+            e.status = self.scan_status
+            raise e
+
+    def scan_dev(self, start: Optional[bytes] = None, first_block: int = 0,
+                 max_blocks: int = 1024, verify: bool = True, caps=(0, 16, 16), stream=None,
+                 device=None):
+        """lgs_table_scan_dev: one window with every array a device tensor
+        (resident tables only).  ``keys`` / ``key_off`` (int64, n + 1) /
+        ``key_len`` (int32, n) / ``vals`` / ``val_off`` / ``val_len`` are
+        build_blocks' input as they stand (16 spare bytes); also
+        ``block_entry_first``, ``block_status`` and the host values
+        ``n``, ``blocks_done``, ``next_block``, ``at_end``, ``index_status``.
+        Complete on the stream when it returns."""
+        torch = _torch()
+        dev = torch.device("cuda") if device is None else device
+        return self._scan_call(_L.lgs_table_scan_dev, dev, verify, start, first_block, max_blocks,
+                               caps, stream)
 
 
 def open_table(file, paranoid_checks: bool = False, internal_keys: bool = False,
