@@ -476,3 +476,47 @@ def test_get_equals_get_host(tab, fixture, big, resident):
             got = t.get(keys, verify=bool(c.verify))
         assert got[0] == want[0], c.name
         assert got[1].tobytes() == want[1].tobytes() and got[2].tobytes() == want[2].tobytes(), c.name
+
+
+# ---- 10. one handle, every kind of call in turn ---------------------------
+
+def test_get_scan_and_get_host_interleaved_on_one_borrowed_handle(tab, fixture):
+    """One borrowed handle serves a get, scans in windows of 2 blocks without
+    and with a start key, and a get_host of the same keys beside it, in turn
+    and twice over: each stages its block read in the leased context's pinned
+    arena, and every result is what lcdb recorded for this table."""
+    import sim_table_scan
+    import table_scan_golden_io as sio
+    sets, cases = fixture
+    c = next(c for c in cases if c.name == "fill256_internal:1")
+    sc = next(s for s in sio.read() if s.name == c.name)
+    file = gio.table_of(c, sets)
+    assert not c.patches and sio.table_of(sc, sets) == file and bool(sc.verify) == bool(c.verify)
+    recs = c.records[::8]
+    keys = [r.key for r in recs]
+    assert 30 <= len(keys) <= 48 and any(r.called for r in recs) and not all(r.called for r in recs)
+    runs = [next(r for r in sc.runs if r.start is None and r.count),
+            next(r for r in sc.runs if r.start is not None and r.count)]
+
+    def check_get(got):
+        res, st, verdict = got
+        for q, r in enumerate(recs):
+            assert table_io.same_outcome(int(st[q]), r.rc), (q, int(st[q]), r.rc)
+            assert res[q] == ((r.found_key, r.found_value) if r.called else None), q
+            assert int(verdict[q]) == (sim.verdict(r.found_key, r.key) if r.called else sim.NOTFOUND), q
+
+    def check_scan(t, r):
+        ents = list(t.scan(start=r.start, verify=bool(c.verify), max_blocks=2))
+        assert table_io.same_outcome(t.scan_status, r.rc)
+        assert len(ents) == r.count and sim_table_scan.digest(ents) == r.digest
+        assert r.entries is None or ents == r.entries
+
+    fname = tab.FILTER_NAME if c.bits_per_key else None
+    with _open_case(tab, c, file, 0) as t:
+        assert t.status == tab.LGS_ST_OK
+        for _ in range(2):
+            check_get(t.get(keys, verify=bool(c.verify)))
+            check_scan(t, runs[0])
+            check_get(tab.get_host(file, keys, verify=bool(c.verify), paranoid_checks=bool(c.paranoid),
+                                   internal_keys=bool(c.internal), filter_name=fname))
+            check_scan(t, runs[1])
