@@ -650,6 +650,94 @@ int lgs_table_scan_dev(lgs_table *table, int verify_checksums, const uint8_t *st
                        uint8_t *d_block_status, uint32_t *blocks_done, uint32_t *next_block,
                        int *at_end, uint8_t *index_status, uint64_t *needed, void *stream);
 
+/* Merging sorted runs: the forward half of lcdb's merging iterator
+ * (src/table/merger.c) and the drop loop of ldb_do_compaction_work
+ * (src/db_impl.c:1363-1397), on entries in the layout the scans above deliver
+ * and lgs_block_cut_dev takes.  With it scan -> merge -> build stays in device
+ * memory.
+ *
+ * A run is the six arrays of lgs_block_entries_emit_dev / lgs_table_scan_dev
+ * plus n: uint64 offsets, uint32 lengths, keys and vals readable 16 bytes past
+ * their end.  The lgs_run array itself is host memory; for the _dev calls its
+ * pointers are device pointers.  0 <= nruns <= LGS_MERGE_MAX_RUNS (more:
+ * LGS_EINVAL), under 2^31 entries in all, per-entry sizes as the builder's.
+ *
+ * Order: what ldb_mergeiter_first followed by ldb_mergeiter_next until
+ * invalid delivers over children positioned on the runs.  The comparator is
+ * bytewise (internal_keys = 0, comparator.c:44-88) or the internal-key
+ * comparator (internal_keys = 1, dbformat.c:232-285: the user key, all but
+ * the last 8 bytes, bytewise; then the trailing fixed64 tag (seq << 8) | type,
+ * descending).  ldb_mergeiter_find_smallest (merger.c:107-128) replaces its
+ * candidate only on a strict `<`: among equal keys the lowest-numbered run's
+ * entry comes first, and within a run the order is the run's own.  Every entry
+ * of every run is delivered; equal keys are not collapsed.
+ *
+ * Preconditions: every run is non-decreasing under the comparator, and with
+ * internal_keys every key has at least 8 bytes (the builder's contract; the
+ * reference asserts it, so db_impl.c:1363-1367's "do not hide error keys"
+ * branch cannot be reached from here).  The plan checks both with a compare
+ * of each entry and its predecessor: d_counts[5] is the lowest-numbered
+ * offending run, or ~0 when there is none.  When it is set the other counts
+ * and everything lgs_merge_emit_dev writes are undefined (but inside the
+ * buffers the counts size); lgs_merge_host returns LGS_EINVAL and writes
+ * nothing.
+ *
+ * Drop rule (drop = 1, internal_keys = 1 only; db_impl.c:1369-1396), walking
+ * the merged order: last_seq is LDB_MAX_SEQUENCE (2^56 - 1) at the first entry
+ * of a user key, otherwise the sequence of the entry just before, dropped or
+ * not.  An entry is dropped when last_seq <= smallest_snapshot (A), or else
+ * when it is a deletion (type 0) with sequence <= smallest_snapshot and
+ * drop_deletions is set.  drop_deletions stands for
+ * ldb_compaction_is_base_level_for_key, which the caller asserts for the
+ * whole call: a caller whose answer differs by key range splits the merge by
+ * range.  With drop = 0 nothing is dropped, and smallest_snapshot and
+ * drop_deletions are ignored.
+ *
+ * Two device calls, as lgs_block_cut_dev / _emit_dev, because the host sizes
+ * the outputs between them.  lgs_merge_plan_dev orders the entries, applies
+ * the rule and writes d_counts[8] = {entries kept, key bytes, value bytes,
+ * longest key, entries dropped, first unsorted-or-short-key run or ~0, 0, 0}.
+ * lgs_merge_emit_dev, given n_out = d_counts[0], writes d_keys (d_counts[1] +
+ * 16 bytes), d_key_off (n_out + 1), d_key_len (n_out), d_vals (d_counts[2] +
+ * 16), d_val_off (n_out + 1), d_val_len (n_out) -- lgs_block_cut_dev's input
+ * as they stand -- and per kept entry the run and the position in it that it
+ * came from, d_src_run and d_src_index (n_out each).  Both take the same runs
+ * (the emit copies from the addresses the plan saw) and the same
+ * lgs_merge_scratch(n_total, nruns) bytes of device scratch (about 85 bytes
+ * per input entry), left alone between them, and both are asynchronous on
+ * `stream`.  The work is ceil(log2 nruns) passes of a binary
+ * search per entry, then one copy of the kept bytes.
+ *
+ * lgs_merge_host: host arrays in and out (a pooled context, one
+ * synchronisation between plan and emit).  needed[5] = {entries kept, key
+ * bytes, value bytes, longest key, entries dropped}; LGS_ENOSPC when
+ * entry_cap, key_cap or val_cap is smaller, and then no entry is written.
+ * key_off and val_off take entry_cap + 1 values. */
+typedef struct lgs_run {
+  const uint8_t *keys;
+  const uint64_t *key_off;
+  const uint32_t *key_len;
+  const uint8_t *vals;
+  const uint64_t *val_off;
+  const uint32_t *val_len;
+  uint32_t n;
+} lgs_run;
+#define LGS_MERGE_MAX_RUNS 64
+size_t lgs_merge_scratch(uint32_t n_total, uint32_t nruns);
+int lgs_merge_plan_dev(const lgs_run *runs, uint32_t nruns, int internal_keys, int drop,
+                       uint64_t smallest_snapshot, int drop_deletions, uint64_t *d_counts,
+                       void *d_scratch, size_t scratch_bytes, void *stream);
+int lgs_merge_emit_dev(const lgs_run *runs, uint32_t nruns, uint32_t n_out, uint8_t *d_keys,
+                       uint64_t *d_key_off, uint32_t *d_key_len, uint8_t *d_vals,
+                       uint64_t *d_val_off, uint32_t *d_val_len, uint32_t *d_src_run,
+                       uint32_t *d_src_index, void *d_scratch, size_t scratch_bytes,
+                       void *stream);
+int lgs_merge_host(const lgs_run *runs, uint32_t nruns, int internal_keys, int drop,
+                   uint64_t smallest_snapshot, int drop_deletions, uint8_t *keys, size_t key_cap,
+                   uint64_t *key_off, uint32_t *key_len, uint8_t *vals, size_t val_cap,
+                   uint64_t *val_off, uint32_t *val_len, uint32_t *src_run, uint32_t *src_index,
+                   uint32_t entry_cap, uint64_t *needed);
+
 /* Devices and diagnostics. */
 /* The drop-in's current footprint: pinned and device bytes held by its
    staging slots, the number of slots created (all devices) and the bytes of

@@ -112,6 +112,14 @@ _SIGS = {
                                      C.c_uint32, _vp, _vp, C.POINTER(C.c_uint32),
                                      C.POINTER(C.c_uint32), C.POINTER(C.c_int),
                                      C.POINTER(C.c_uint8), _vp, _vp]),
+    "lgs_merge_scratch": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "lgs_merge_plan_dev": (C.c_int, [_vp, C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.c_int, _vp,
+                                     _vp, C.c_size_t, _vp]),
+    "lgs_merge_emit_dev": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, C.c_size_t, _vp]),
+    "lgs_merge_host": (C.c_int, [_vp, C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.c_int, _vp,
+                                 C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp,
+                                 C.c_uint32, _vp]),
     "lgs_dropin_footprint": (C.c_int, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                        C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]),
     "lgs_service_quiesce": (C.c_int, []),
@@ -123,6 +131,15 @@ _SIGS = {
     "lgs_last_error": (C.c_char_p, []),
     "lgs_version": (C.c_char_p, []),
 }
+
+LGS_MERGE_MAX_RUNS = 64
+
+
+class LgsRun(C.Structure):
+    """lgs_run: one sorted run of lgs_merge_* (host or device pointers)."""
+    _fields_ = [("keys", _vp), ("key_off", _vp), ("key_len", _vp), ("vals", _vp),
+                ("val_off", _vp), ("val_len", _vp), ("n", C.c_uint32)]
+
 
 # Every symbol include/lcdb_gpu_snappy.h declares.
 EXPORTED = tuple(_SIGS)

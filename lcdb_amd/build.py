@@ -29,10 +29,11 @@ PROBE_SOURCES = ["lgs_decode_probe.hip", "lgs_decode_group.hip", "lgs_decode_cha
 
 HIP_SOURCES = ["lgs_api.cpp", "lgs_table_api.cpp", "lgs_encode_service.hip", "lgs_decode.hip",
                "lgs_table.hip", "lgs_bloom.hip", "lgs_table_index.cpp", "lgs_probe.hip",
-               "lgs_block.hip", "lgs_table_tail.cpp", "lgs_seek.hip", "lgs_scan.hip"]
+               "lgs_block.hip", "lgs_table_tail.cpp", "lgs_seek.hip", "lgs_scan.hip",
+               "lgs_merge_api.cpp", "lgs_merge.hip"]
 HIP_HEADERS = ["lgs_device.h", "lgs_launch.h", "lgs_decode_common.h", "lgs_probe_hooks.h",
                "lgs_service.h", "lgs_crc.h", "lgs_block.h", "lgs_table_tail.h",
-               "lgs_seek.h", "lgs_scan.h", "lgs_host.h"]
+               "lgs_seek.h", "lgs_scan.h", "lgs_host.h", "lgs_merge.h", "lgs_span.h"]
 # Only ldb_snappy_* and lgs_* are exported (the library is loaded into lcdb).
 EXPORTS_MAP = os.path.join(CSRC, "exports.map")
 # The files that define the two profiled codec kernels and how they are

@@ -17,14 +17,14 @@
 
 #include "lgs_device.h"
 #include "lgs_scan.h"
+#include "lgs_span.h"
 
 namespace lgs {
 
 namespace {
 
-constexpr uint32_t kGroup = 16;   // lanes per entry in the copy
+constexpr uint32_t kGroup = kSpanLanes;   // lanes per entry in the copy (copy_span, lgs_span.h)
 
-typedef u32x4 u32x4_a1 __attribute__((aligned(1)));
 using bytes_g = gptr<const uint8_t>;
 
 __device__ __forceinline__ uint32_t ld_le32(bytes_g p) {
@@ -237,22 +237,6 @@ __global__ __launch_bounds__(256) void entries_walk_kernel(EntriesIn a,
   const uint32_t b = blockIdx.x * 256 + threadIdx.x;
   if (b >= a.nblocks) return;
   (void)walk_block<true>(a, b, wfirst[b], dfirst[b], o);
-}
-
-// len bytes from s to d by the kGroup lanes of a group (lane gl): the whole
-// 16-byte destination granules with one unaligned load and one aligned store
-// each, and the ragged ends (under 16 bytes each) a byte per lane, so a short
-// span is one store instruction of the group instead of a loop of one lane
-// (keys are mostly short spans: a delta, and a prefix piece per link).  Reads
-// and writes stay inside [s, s + len) and [d, d + len).
-__device__ __forceinline__ void copy_span(bytes_g s, gptr<uint8_t> d, uint32_t len, uint32_t gl) {
-  const uint32_t lead = (16u - (uint32_t)((uintptr_t)d & 15u)) & 15u;
-  const uint32_t head = lead < len ? lead : len;
-  if (gl < head) d[gl] = s[gl];
-  const uint32_t mid = (len - head) & ~15u, body = head + mid;
-  for (uint32_t k = head + 16u * gl; k < body; k += 16u * kGroup)
-    *(gptr<u32x4>)(d + k) = *(gptr<const u32x4_a1>)(s + k);
-  if (gl < len - body) d[body + gl] = s[body + gl];
 }
 
 __global__ __launch_bounds__(256) void entries_copy_kernel(

@@ -27,6 +27,11 @@ the batched C ABI that does both for many blocks per launch
   411-415): their entries in ``build_blocks``' input layout;
 * ``OpenTable.scan`` / ``.scan_dev`` -- ``ldb_tableiter_create``, first or
   seek, next until invalid (src/table/two_level_iterator.c, table.c:229-311);
+* ``merge_runs`` / ``merge_runs_host`` -- ``ldb_mergeiter_first`` + ``_next``
+  until invalid over sorted runs (src/table/merger.c) and the drop loop of
+  ``ldb_do_compaction_work`` (src/db_impl.c:1369-1396);
+* ``compact_tables``  -- scan, merge and drop, build: one compaction's output
+  table from its input tables;
 * ``index_host``      -- ``ldb_table_open``'s footer, index-block handles and
   metaindex filter handle (src/table/table.c:78-180), the handles the batched
   read takes.
@@ -50,7 +55,7 @@ _L = _native.lib()
 
 __all__ = [
     "crc32c_batch", "write_blocks", "read_blocks", "write_blocks_host", "read_blocks_host",
-    "index_host", "FILTER_NAME", "seek_blocks_host", "block_entries", "block_entries_host", "ScanError", "get_host", "open_table", "OpenTable", "build_blocks", "build_blocks_host", "build_table_host",
+    "index_host", "FILTER_NAME", "seek_blocks_host", "block_entries", "block_entries_host", "ScanError", "merge_runs", "merge_runs_host", "compact_tables", "MergeError", "get_host", "open_table", "OpenTable", "build_blocks", "build_blocks_host", "build_table_host",
     "LGS_NO_COMPRESSION", "LGS_SNAPPY_COMPRESSION", "LGS_TRAILER_SIZE", "LGS_ST_OK",
     "LGS_ST_CORRUPT", "LGS_ST_NOSPACE", "LGS_ST_IOERR", "LGS_ST_BADCRC", "LGS_ST_BADTYPE",
     "LGS_GET_NOTFOUND", "LGS_GET_FOUND", "LGS_GET_DELETED", "LGS_GET_CORRUPT",
@@ -818,3 +823,170 @@ def open_table(file, paranoid_checks: bool = False, internal_keys: bool = False,
     image is borrowed: pass a numpy uint8 array and keep it unchanged in its
     data blocks while the table is open (bytes are copied once instead)."""
     return OpenTable(file, paranoid_checks, internal_keys, filter_name, resident)
+
+
+# ---------------------------------------------------------------------------
+# Merging sorted runs (lgs_merge_*).
+# ---------------------------------------------------------------------------
+
+class MergeError(_native.LgsError):
+    """A merge the library refused: ``.rc`` (LGS_EINVAL for a run that is not
+    sorted or holds a short internal key, then ``.run`` names it where known;
+    LGS_ENOSPC for outputs too small, then ``.needed`` and ``.untouched``)."""
+
+
+_NO_RUN = (1 << 64) - 1
+
+
+def merge_runs(runs, internal_keys: bool = False, drop: bool = False, smallest_snapshot: int = 0,
+               drop_deletions: bool = False, stream=None):
+    """ldb_mergeiter_first + _next until invalid over sorted runs in device
+    memory, then (``drop``, internal keys only) compaction's drop rule
+    (lgs_merge_plan_dev + one read-back of the counts + lgs_merge_emit_dev).
+
+    A run is a dict as ``block_entries`` / ``OpenTable.scan_dev`` return it:
+    ``keys``, ``key_off``, ``key_len``, ``vals``, ``val_off``, ``val_len`` and
+    optionally ``n``.  Among equal keys the lowest-numbered run comes first.
+    Returns the same dict shape (``build_blocks``' input as it stands) plus
+    ``src_run`` / ``src_index`` (int32, per kept entry) and the ints ``n``,
+    ``dropped``, ``key_bytes``, ``val_bytes``, ``max_key``.  Raises MergeError
+    for a run that is not sorted.  The runs must stay alive until the stream
+    has passed the call."""
+    torch = _torch()
+    k = len(runs)
+    arr = (_native.LgsRun * max(k, 1))()
+    n_total = 0
+    dev = None
+    for r, run in enumerate(runs):
+        n = int(run["n"]) if "n" in run else int(run["key_len"].numel())
+        dev = run["keys"].device if dev is None else dev
+        arr[r] = _native.LgsRun(*(run[f].data_ptr() for f in
+                                  ("keys", "key_off", "key_len", "vals", "val_off", "val_len")), n)
+        n_total += n
+    dev = torch.device("cuda") if dev is None else dev
+    sp = _stream_ptr(stream)
+    scr = torch.empty(max(int(_L.lgs_merge_scratch(min(n_total, 0x7fffffff),
+                                                   min(k, _native.LGS_MERGE_MAX_RUNS))), 1),
+                      dtype=torch.uint8, device=dev)
+    counts = torch.empty(8, dtype=torch.int64, device=dev)
+    check(_L.lgs_merge_plan_dev(arr, k, 1 if internal_keys else 0, 1 if drop else 0,
+                                int(smallest_snapshot), 1 if drop_deletions else 0,
+                                counts.data_ptr(), scr.data_ptr(), int(scr.numel()), sp),
+          "lgs_merge_plan_dev")
+    if stream is not None:
+        stream.synchronize()
+    cnt = [int(x) & _NO_RUN for x in counts.cpu()]
+    if cnt[5] != _NO_RUN:
+        e = MergeError(f"lgs_merge_plan_dev: run {cnt[5]} is not sorted or has a short key")
+        e.rc, e.run = _native.LGS_EINVAL, cnt[5]
+        raise e
+    n, kb, vb, mk, dropped = cnt[:5]
+    keys = torch.empty(kb + 16, dtype=torch.uint8, device=dev)
+    vals = torch.empty(vb + 16, dtype=torch.uint8, device=dev)
+    key_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    val_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    i32 = lambda: torch.empty(max(n, 1), dtype=torch.int32, device=dev)   # noqa: E731
+    key_len, val_len, src_run, src_index = i32(), i32(), i32(), i32()
+    check(_L.lgs_merge_emit_dev(arr, k, n, keys.data_ptr(), key_off.data_ptr(),
+                                key_len.data_ptr(), vals.data_ptr(), val_off.data_ptr(),
+                                val_len.data_ptr(), src_run.data_ptr(), src_index.data_ptr(),
+                                scr.data_ptr(), int(scr.numel()), sp), "lgs_merge_emit_dev")
+    if stream is not None:
+        scr.record_stream(stream)
+    return {"keys": keys, "key_off": key_off, "key_len": key_len[:n], "vals": vals,
+            "val_off": val_off, "val_len": val_len[:n], "src_run": src_run[:n],
+            "src_index": src_index[:n], "n": n, "dropped": dropped, "key_bytes": kb,
+            "val_bytes": vb, "max_key": mk}
+
+
+def merge_runs_host(runs, internal_keys: bool = False, drop: bool = False,
+                    smallest_snapshot: int = 0, drop_deletions: bool = False, caps=None):
+    """lgs_merge_host on lists of (key, value): returns ([(key, value)],
+    [(run, index)], dropped).  caps: (entries, key bytes, value bytes) to call
+    with; by default one call with nothing sizes the outputs.  Raises
+    MergeError (``.rc``) where the call returns LGS_EINVAL or LGS_ENOSPC."""
+    k = len(runs)
+    arr = (_native.LgsRun * max(k, 1))()
+    packed = []
+    for r, run in enumerate(runs):
+        a = _pack_entries(run)
+        packed.append(a)
+        arr[r] = _native.LgsRun(*(x.ctypes.data for x in a), len(run))
+    needed = np.zeros(5, dtype=np.uint64)
+
+    def call(n, kb, vb):
+        out = (np.zeros(kb + 16, dtype=np.uint8), np.zeros(n + 1, dtype=np.uint64),
+               np.zeros(max(n, 1), dtype=np.uint32), np.zeros(vb + 16, dtype=np.uint8),
+               np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint32),
+               np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32))
+        keys, koff, klen, vals, voff, vlen, srun, sidx = out
+        rc = _L.lgs_merge_host(arr, k, 1 if internal_keys else 0, 1 if drop else 0,
+                               int(smallest_snapshot), 1 if drop_deletions else 0,
+                               keys.ctypes.data, kb, koff.ctypes.data, klen.ctypes.data,
+                               vals.ctypes.data, vb, voff.ctypes.data, vlen.ctypes.data,
+                               srun.ctypes.data, sidx.ctypes.data, n, needed.ctypes.data)
+        return rc, out
+
+    rc, out = call(*(caps if caps is not None else (0, 0, 0)))
+    if rc == LGS_ENOSPC and caps is None:
+        rc, out = call(*(int(x) for x in needed[:3]))
+    if rc != _native.LGS_OK:
+        msg = _L.lgs_last_error().decode(errors="replace")
+        e = MergeError(f"lgs_merge_host failed ({rc}): {msg}")
+        e.rc = rc
+        e.needed = tuple(int(x) for x in needed)
+        e.untouched = not any(a.any() for a in out)
+        raise e
+    n = int(needed[0])
+    entries = _unpack_entries(*out[:6], n)
+    return entries, [(int(out[6][i]), int(out[7][i])) for i in range(n)], int(needed[4])
+
+
+def compact_tables(tables, smallest_snapshot: int, drop_deletions: bool, block_size: int = 4096,
+                   restart_interval: int = 16, compression: int = LGS_SNAPPY_COMPRESSION,
+                   bits_per_key: int = 0, verify: bool = True) -> bytes:
+    """One compaction's output table from its input table images, in the
+    order ldb_inputiter_create hands them to the merging iterator (newest
+    level-0 file first): ``OpenTable.scan_dev`` per table, ``merge_runs``
+    with internal keys and the drop rule, then ``build_table_host``.
+
+    ``drop_deletions`` is ldb_compaction_is_base_level_for_key for every key
+    of the call.  The whole output is one file: should_stop_before and
+    max_output_file_size are not applied.  Between the merge and the build
+    the kept entries make one round trip through host memory; a build entry
+    point that takes entries in device memory is what removes it."""
+    torch = _torch()
+    runs, opened = [], []
+    try:
+        for img in tables:
+            t = open_table(img, internal_keys=True, resident=True,
+                           filter_name=FILTER_NAME if bits_per_key else None)
+            opened.append(t)
+            nxt = 0
+            while True:
+                r = t.scan_dev(first_block=nxt, max_blocks=65536, verify=verify)
+                bad = r["index_status"] if r["at_end"] else LGS_ST_OK
+                if bad == LGS_ST_OK and r["blocks_done"]:
+                    st = r["block_status"].cpu().numpy()
+                    bad = LGS_ST_OK if (st == LGS_ST_OK).all() else int(st[st != LGS_ST_OK][0])
+                if bad != LGS_ST_OK:
+                    e = ScanError(f"compaction input ended with status {bad}")
+                    e.status = bad
+                    raise e
+                runs.append(r)
+                nxt = r["next_block"]
+                if r["at_end"]:
+                    break
+        m = merge_runs(runs, internal_keys=True, drop=True, smallest_snapshot=smallest_snapshot,
+                       drop_deletions=drop_deletions)
+        torch.cuda.synchronize()
+        n = m["n"]
+        entries = _unpack_entries(m["keys"].cpu().numpy(), m["key_off"].cpu().numpy(),
+                                  m["key_len"].cpu().numpy().view(np.uint32),
+                                  m["vals"].cpu().numpy(), m["val_off"].cpu().numpy(),
+                                  m["val_len"].cpu().numpy().view(np.uint32), n)
+    finally:
+        for t in opened:
+            t.close()
+    return build_table_host(entries, block_size, restart_interval, compression, bits_per_key,
+                            internal_keys=True)
