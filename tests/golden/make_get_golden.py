@@ -58,12 +58,12 @@ def case_file(path: str, internal: int, bits: int, paranoid: int, verify: int, k
             f.write(struct.pack("<I", len(k)) + k)
 
 
-def run_driver(driver: str, tmp: str, table: bytes, c: Case, keys) -> None:
+def run_driver(driver: str, tmp: str, table: bytes, c: Case, keys, timeout=None) -> None:
     tp, cp, op = (os.path.join(tmp, n) for n in ("t.ldb", "case", "out"))
     with open(tp, "wb") as f:
         f.write(table)
     case_file(cp, c.internal, c.bits_per_key, c.paranoid, c.verify, keys)
-    r = subprocess.run([driver, tp, cp, op], capture_output=True, text=True)
+    r = subprocess.run([driver, tp, cp, op], capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stdout + r.stderr
     b = open(op, "rb").read()
     (c.open_rc,) = struct.unpack_from("<i", b, 0)

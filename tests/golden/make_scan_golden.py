@@ -47,7 +47,7 @@ def compile_driver(tmp: str) -> str:
     return driver
 
 
-def run_driver(driver: str, tmp: str, table: bytes, c: Case, seeks) -> None:
+def run_driver(driver: str, tmp: str, table: bytes, c: Case, seeks, timeout=None) -> None:
     tp, cp, op = (os.path.join(tmp, n) for n in ("t.ldb", "case", "out"))
     with open(tp, "wb") as f:
         f.write(table)
@@ -55,7 +55,7 @@ def run_driver(driver: str, tmp: str, table: bytes, c: Case, seeks) -> None:
         f.write(struct.pack("<5I", c.internal, c.bits_per_key, c.paranoid, c.verify, len(seeks)))
         for k in seeks:
             f.write(struct.pack("<I", len(k)) + k)
-    r = subprocess.run([driver, tp, cp, op], capture_output=True, text=True)
+    r = subprocess.run([driver, tp, cp, op], capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stdout + r.stderr
     b = open(op, "rb").read()
     (c.open_rc,) = struct.unpack_from("<i", b, 0)

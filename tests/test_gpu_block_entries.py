@@ -195,6 +195,34 @@ def test_hostile_block_output(tab):
     assert sts == [1] and len(ents[0]) == 350 and len(ents[0][299][0]) == 300
 
 
+@pytest.mark.parametrize("internal", [0, 1])
+def test_damaged_blocks(tab, sets, internal):
+    """The randomly damaged data blocks of test_table_get_sim.damaged_blocks in
+    one call, every second one walked and delivered from offsets chosen among
+    the headers the model finds; boundary_blocks' headers between
+    decode_entry's two paths; with the bytewise ones 20 copies of the hostile
+    block with 1 to 5 damaged bytes."""
+    import random
+    from test_table_get_sim import boundary_blocks, damage_block, damaged_blocks
+    rng = random.Random(77 + internal)
+    blocks = [d for d, _ in damaged_blocks(sets, bool(internal))]
+    assert len(blocks) >= 200
+    blocks += [d for d, _ in boundary_blocks(bool(internal))]
+    if not internal:
+        blocks += [damage_block(rng, hostile_block(2000)) for _ in range(20)]
+    walk_from, emit_from = [], []
+    for i, d in enumerate(blocks):
+        _, heads = sim._headers(d, bool(internal), None)
+        wf = ef = None
+        if heads and i % 2:
+            wf = rng.choice(heads)[0]
+            ef = rng.choice([h[0] for h in heads if h[0] >= wf])
+        walk_from.append(wf)
+        emit_from.append(ef)
+    ents, sts = both(tab, blocks, bool(internal), walk_from=walk_from, emit_from=emit_from)
+    assert sum(st != sim.ST_OK for st in sts) >= 20 and sum(len(e) for e in ents) > 1000
+
+
 def test_walk_from_and_emit_from(tab, sets):
     """A block damaged before a later restart point: the walk from restart[0]
     ends at the damage, a walk begun at the later run does not meet it, and

@@ -171,6 +171,69 @@ def test_keys_sharing_a_16_byte_prefix(tab):
         assert got[0] == want[0] and got[1] == want[1]
 
 
+def binary_users(rng, count: int):
+    """`count` distinct user keys over the alphabet a, \\0, \\xff at lengths 0,
+    1, 7, 8, 9, 15, 16 and 17: cuts of four base strings with up to two bytes
+    changed, so that keys agree up to any position, differ in a byte before,
+    in or behind the first 8, and are each other's prefixes padded with \\0."""
+    alphabet = (0x61, 0x00, 0xff)
+    bases = [bytes(rng.choice(alphabet) for _ in range(17)) for _ in range(4)]
+    users = {b""}
+    while len(users) < count:
+        u = bytearray(rng.choice(bases)[:rng.choice((1, 7, 8, 9, 15, 16, 17))])
+        for _ in range(rng.randrange(3)):
+            u[rng.randrange(len(u))] = rng.choice(alphabet)
+        users.add(bytes(u))
+    return sorted(users)
+
+
+def run_of(i: int, k: int) -> int:
+    """Run r takes r + 1 of every 1 + 2 + ... + k entries."""
+    x = (i * 7 + i // 5) % (k * (k + 1) // 2)
+    return next(r for r in range(k) if x < (r + 1) * (r + 2) // 2)
+
+
+@pytest.mark.parametrize("k", [2, 3, 5])
+def test_binary_keys(tab, k):
+    """About 600 distinct keys of \\0, \\xff and `a` bytes around the 8-byte
+    word, dealt over k runs of unequal size with equal user keys in different
+    runs: entries, sources and dropped counts equal the model's, plain and
+    with the compaction drop at every snapshot."""
+    import random
+    rng = random.Random(600 + k)
+    # Bytewise: every third key also in the next run (ties across runs).
+    runs = [[] for _ in range(k)]
+    for i, u in enumerate(binary_users(rng, 600)):
+        r = run_of(i, k)
+        runs[r].append((u, b"%d" % i))
+        if i % 3 == 0:
+            runs[(r + 1) % k].append((u, b"dup%d" % i))
+    runs = [sorted(r, key=sim.sort_key(False)) for r in runs]
+    assert len({len(r) for r in runs}) == k
+    want = sim.merge(runs, False)
+    got = both(tab, runs, internal_keys=False)
+    assert got[0] == want[0] and got[1] == want[1] and got[2] == 0
+    # Internal: versions (seq 0..3, type 0 / 1) of one user key in different runs.
+    runs = [[] for _ in range(k)]
+    n = 0
+    for i, u in enumerate(binary_users(rng, 220)):
+        r = run_of(i, k)
+        for j, seq in enumerate(rng.sample(range(4), rng.randint(1, 4))):
+            runs[(r + j) % k].append((ikey(u, seq, rng.randrange(2)), b"%d.%d" % (i, seq)))
+            n += 1
+    runs = [sorted(r, key=sim.sort_key(True)) for r in runs]
+    assert 500 <= n <= 700 and len({len(r) for r in runs}) == k
+    want = sim.merge(runs, True)
+    got = both(tab, runs, internal_keys=True)
+    assert got[0] == want[0] and got[1] == want[1] and got[2] == 0
+    for snap in (0, 1, 2, 3):
+        for dd in (False, True):
+            want = sim.merge(runs, True, True, snap, dd)
+            got = both(tab, runs, internal_keys=True, drop=True, smallest_snapshot=snap,
+                       drop_deletions=dd)
+            assert got[0] == want[0] and got[1] == want[1] and got[2] == want[2], (snap, dd)
+
+
 def test_one_entry_against_five_thousand(tab):
     big = [(b"key%08d" % (2 * i), b"") for i in range(5000)]
     for one in (b"key%08d" % 4999, b"key%08d" % 5000, b"", b"zzz"):

@@ -12,6 +12,7 @@ import sys
 import numpy as np
 import pytest
 
+import damage_golden_io as dio
 import table_get_golden_io as gio
 import table_golden_io
 import table_io
@@ -52,16 +53,37 @@ def _check_case(tab, c, file):
             assert int(verdict[q]) == want, what
 
 
-@pytest.mark.parametrize("group", ["bytewise", "internal", "patched"])
+def _check_unopened(tab, c, file, keys):
+    """A table lcdb did not open: its open status (under the INTEGRATION §3.1
+    mapping) for every lookup, and nothing found."""
+    fname = tab.FILTER_NAME if c.bits_per_key else None
+    want = tab.index_host(file, paranoid_checks=bool(c.paranoid), internal_keys=bool(c.internal),
+                          filter_name=fname)[3]
+    assert table_io.same_outcome(want, c.open_rc), (c.name, want, c.open_rc)
+    res, st, verdict = tab.get_host(file, keys, verify=bool(c.verify),
+                                    paranoid_checks=bool(c.paranoid),
+                                    internal_keys=bool(c.internal), filter_name=fname)
+    assert res == [None] * len(keys) and list(st) == [want] * len(keys), c.name
+    assert not verdict.any(), c.name
+
+
+@pytest.mark.parametrize("group", ["bytewise", "internal", "patched", "damaged"])
 def test_get_host_equals_the_reference(tab, fixture, group):
     """One lgs_table_get_host call per fixture table: called, status (under
     the INTEGRATION §3.1 mapping), key and value bytes as lcdb returned them;
-    the verdict against save_value's rule on lcdb's recorded key."""
+    the verdict against save_value's rule on lcdb's recorded key.  "damaged":
+    the randomly damaged tables of damage_get.bin, the ones lcdb did not open
+    among them."""
     sets, cases = fixture
     n = 0
-    for c in cases:
+    for c in (dio.read_get() if group == "damaged" else cases):
         g = "patched" if c.patches else ("internal" if c.internal else "bytewise")
-        if g != group:
+        if group != "damaged" and g != group:
+            continue
+        if group == "damaged" and c.open_rc != table_io.LDB_OK:
+            s = next(s for s in sets if s.name == c.set_name)
+            _check_unopened(tab, c, gio.table_of(c, sets), [k for k, _ in s.entries[:3]])
+            n += 1
             continue
         assert c.open_rc == table_io.LDB_OK
         _check_case(tab, c, gio.table_of(c, sets))
@@ -127,6 +149,35 @@ def test_seek_blocks_equals_the_model(tab, fixture, internal):
             assert res[q] == (e[0], e[1], blk[e[2]:e[2] + e[3]]), (q, b, k[:40])
             hits += 1
     assert hits > 1000
+
+
+@pytest.mark.parametrize("internal", [0, 1])
+def test_seek_blocks_on_damaged_blocks(tab, fixture, internal):
+    """lgs_block_seek_dev in one call on the randomly damaged data blocks of
+    test_table_get_sim.damaged_blocks (over 400 for the two key kinds
+    together, 6 to 10 targets each; the version blocks for internal keys) and
+    on boundary_blocks' headers between decode_entry's two paths: status, entry position, key and value as sim_table_get.block_seek has
+    them."""
+    from test_table_get_sim import boundary_blocks, damaged_blocks
+    sets, _ = fixture
+    batch = damaged_blocks(sets, bool(internal))
+    assert len(batch) >= 200
+    batch += boundary_blocks(bool(internal))
+    blocks = [d for d, _ in batch]
+    queries = [(b, k) for b, (_, keys) in enumerate(batch) for k in keys]
+    res, st = tab.seek_blocks_host(blocks, queries, internal_keys=bool(internal))
+    hits = bad = 0
+    for q, (b, k) in enumerate(queries):
+        want_st, e = sim.block_seek(blocks[b], k, bool(internal))
+        assert int(st[q]) == want_st, (q, b, k[:40])
+        bad += want_st != sim.ST_OK
+        if e is None:
+            assert res[q] is None, (q, b, k[:40])
+        else:
+            blk = blocks[b]
+            assert res[q] == (e[0], e[1], blk[e[2]:e[2] + e[3]]), (q, b, k[:40])
+            hits += 1
+    assert hits > 500 and bad > 50
 
 
 def sets_variant(sets, c):

@@ -15,6 +15,7 @@ import threading
 import numpy as np
 import pytest
 
+import damage_golden_io as dio
 import table_get_golden_io as gio
 import table_golden_io
 import table_io
@@ -112,16 +113,37 @@ def _open_case(tab, c, file, resident):
 
 # ---- 1. reference parity -------------------------------------------------
 
+def _cases_of(cases, group):
+    """The fixture's cases of one group; "damaged": the randomly damaged tables
+    of damage_get.bin, the ones lcdb did not open among them."""
+    if group == "damaged":
+        return dio.read_get()
+    return [c for c in cases if _group_of(c) == group]
+
+
+def _some_keys(sets, c):
+    return [k for k, _ in next(s for s in sets if s.name == c.set_name).entries[:3]]
+
+
 @pytest.mark.parametrize("resident", [0, 1])
-@pytest.mark.parametrize("group", ["bytewise", "internal", "patched"])
+@pytest.mark.parametrize("group", ["bytewise", "internal", "patched", "damaged"])
 def test_get_equals_the_reference(tab, fixture, group, resident):
     """Every fixture case through one opened handle with one get: called,
     status (under the INTEGRATION §3.1 mapping), key and value bytes as lcdb
-    returned them; the verdict against save_value's rule on lcdb's key."""
+    returned them; the verdict against save_value's rule on lcdb's key.  A
+    table lcdb did not open: its open status, and nothing found."""
     sets, cases = fixture
     n = 0
-    for c in cases:
-        if _group_of(c) != group:
+    for c in _cases_of(cases, group):
+        if group == "damaged" and c.open_rc != table_io.LDB_OK:
+            keys = _some_keys(sets, c)
+            with _open_case(tab, c, gio.table_of(c, sets), resident) as t:
+                assert table_io.same_outcome(t.status, c.open_rc), (c.name, t.status, c.open_rc)
+                assert t.info()["status"] == t.status and t.info()["index_bytes"] == 0
+                res, st, verdict = t.get(keys, verify=bool(c.verify))
+                assert res == [None] * len(keys) and list(st) == [t.status] * len(keys), c.name
+                assert not verdict.any(), c.name
+            n += 1
             continue
         assert c.open_rc == table_io.LDB_OK
         with _open_case(tab, c, gio.table_of(c, sets), resident) as t:
@@ -195,17 +217,15 @@ def _same_arrays(a, b, n, total):
     assert a["out"][:total].tobytes() == b["out"][:total].tobytes()
 
 
-@pytest.mark.parametrize("group", ["bytewise", "internal", "patched"])
+@pytest.mark.parametrize("group", ["bytewise", "internal", "patched", "damaged"])
 def test_get_dev_equals_get(tab, native, fixture, group):
     """lgs_table_get_dev on a resident handle: every output, downloaded, is
     lgs_table_get's on the same handle byte for byte, out_key_off, out_val_off
     and out_needed included."""
     sets, cases = fixture
     n = 0
-    for c in cases:
-        if _group_of(c) != group:
-            continue
-        keys = [r.key for r in c.records]
+    for c in _cases_of(cases, group):
+        keys = [r.key for r in c.records] or _some_keys(sets, c)
         cap = sum(len(r.found_key) + len(r.found_value) for r in c.records if r.called)
         with _open_case(tab, c, gio.table_of(c, sets), 1) as t:
             rc, need, a = _raw_get(native, t, keys, cap, verify=c.verify)

@@ -10,6 +10,7 @@ import threading
 import numpy as np
 import pytest
 
+import damage_golden_io as dio
 import table_golden_io
 import table_io
 import table_scan_golden_io as gio
@@ -64,17 +65,27 @@ def _group_of(c):
 
 
 @pytest.mark.parametrize("resident", [0, 1])
-@pytest.mark.parametrize("group", ["bytewise", "internal", "patched"])
+@pytest.mark.parametrize("group", ["bytewise", "internal", "patched", "damaged"])
 def test_scan_equals_the_reference(tab, fixture, group, resident):
     """Every run of every fixture case (the full scan and the recorded seeks,
     the flipped-payload cases verified and unverified among them) in one
-    window, and the full scan and the first seek a block at a time."""
+    window, and the full scan and the first seek a block at a time.
+    "damaged": the randomly damaged tables of damage_scan.bin; one that lcdb
+    did not open has its open status and no entries."""
     sets, cases = fixture
     n = 0
-    for c in cases:
-        if _group_of(c) != group:
+    for c in (dio.read_scan() if group == "damaged" else cases):
+        if group != "damaged" and _group_of(c) != group:
             continue
         with _open_case(tab, c, gio.table_of(c, sets), resident) as t:
+            if group == "damaged" and c.open_rc != table_io.LDB_OK:
+                assert table_io.same_outcome(t.status, c.open_rc), (c.name, t.status, c.open_rc)
+                for w in (4096, 1):
+                    assert _scan(tab, t, verify=bool(c.verify), max_blocks=w) == (t.status, []), c.name
+                r = t.scan_window(b"k" * 9)
+                assert r["at_end"] and r["blocks_done"] == 0 and r["entries"] == [], c.name
+                n += 1
+                continue
             assert t.status == tab.LGS_ST_OK, c.name
             for i, r in enumerate(c.runs):
                 st, ents = _scan(tab, t, start=r.start, verify=bool(c.verify), max_blocks=4096)
@@ -86,6 +97,31 @@ def test_scan_equals_the_reference(tab, fixture, group, resident):
     assert n >= 100
 
 
+def _windows_equal_the_model(tab, c, file, width):
+    """scan_window's own results for every run of case c in windows of
+    `width` blocks (wider where a seek's side walk needs it, as the C call
+    asks) against sim.scan_window."""
+    mt = simget.Table(file, bool(c.paranoid), bool(c.internal), None)
+    lst = sim.IndexList(mt)
+    with _open_case(tab, c, file, 1) as t:
+        for r in c.runs:
+            nxt, first = 0, True
+            while True:
+                start = r.start if first else None
+                want = sim.scan_window(mt, lst, bool(c.verify), start, nxt, width)
+                if "need_blocks" in want:
+                    want = sim.scan_window(mt, lst, bool(c.verify), start, nxt, want["need_blocks"])
+                got = t.scan_window(start, nxt, width, bool(c.verify))
+                for k in ("entries", "blocks_done", "next_block", "at_end"):
+                    assert got[k] == want[k], (c.name, r.start, k)
+                assert [int(x) for x in got["block_entry_first"]] == want["block_entry_first"]
+                assert [int(x) for x in got["block_status"]] == want["block_status"]
+                if want["at_end"]:
+                    assert got["index_status"] == want["index_status"]
+                    break
+                nxt, first = want["next_block"], False
+
+
 def test_windows_and_next_block(tab, fixture):
     """scan_window's own results: block_entry_first, block_status, next_block
     and at_end for windows of 7 blocks equal the model's."""
@@ -94,23 +130,18 @@ def test_windows_and_next_block(tab, fixture):
         if c.name not in ("fill256:3", "fill4096:damage_before_later_restart",
                           "fill256:index_seek_off_walk", "fill4096:index_value_no_handle"):
             continue
-        file = gio.table_of(c, sets)
-        mt = simget.Table(file, bool(c.paranoid), bool(c.internal), None)
-        lst = sim.IndexList(mt)
-        with _open_case(tab, c, file, 1) as t:
-            for r in c.runs:
-                nxt, first = 0, True
-                while True:
-                    want = sim.scan_window(mt, lst, bool(c.verify), r.start if first else None, nxt, 7)
-                    got = t.scan_window(r.start if first else None, nxt, 7, bool(c.verify))
-                    for k in ("entries", "blocks_done", "next_block", "at_end"):
-                        assert got[k] == want[k], (c.name, r.start, k)
-                    assert [int(x) for x in got["block_entry_first"]] == want["block_entry_first"]
-                    assert [int(x) for x in got["block_status"]] == want["block_status"]
-                    if want["at_end"]:
-                        assert got["index_status"] == want["index_status"]
-                        break
-                    nxt, first = want["next_block"], False
+        _windows_equal_the_model(tab, c, gio.table_of(c, sets), 7)
+
+
+def test_windows_and_next_block_on_damaged_index_blocks(tab, fixture):
+    """The same on the tables of damage_scan.bin whose index block is damaged."""
+    sets, _ = fixture
+    n = 0
+    for c in dio.read_scan():
+        if dio.class_of(c) == "index_block" and c.open_rc == table_io.LDB_OK:
+            _windows_equal_the_model(tab, c, gio.table_of(c, sets), 7)
+            n += 1
+    assert n >= 8
 
 
 @pytest.mark.parametrize("resident", [0, 1])

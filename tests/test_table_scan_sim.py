@@ -10,6 +10,7 @@ import random
 import struct
 import sys
 
+import damage_golden_io as dio
 import table_get_golden_io as ggio
 import table_golden_io
 import table_io
@@ -66,6 +67,24 @@ def test_scan_reproduces_every_fixture_run():
             _check(c, r, st, ents)
             n += 1
     assert n > 400
+
+
+def test_scan_reproduces_every_damage_run():
+    """The damaged tables: open status, then sim.scan and the windowed scan at
+    windows of 1, 7 and everything against every recorded run."""
+    n = 0
+    for c in dio.read_scan():
+        t = _table(c)
+        assert table_io.same_outcome(t.status, c.open_rc), (c.name, t.status, c.open_rc)
+        if c.open_rc:
+            assert sim.scan(t, bool(c.verify)) == (t.status, [])
+            assert sim.scan_windows(t, bool(c.verify), None, 7) == (t.status, [])
+        for r in c.runs:
+            _check(c, r, *sim.scan(t, bool(c.verify), r.start))
+            for w in (1, 7, 1 << 20):
+                _check(c, r, *sim.scan_windows(t, bool(c.verify), r.start, w))
+            n += 1
+    assert n > 200
 
 
 def test_unpatched_scan_is_the_entry_list():
