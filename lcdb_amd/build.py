@@ -22,10 +22,11 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "liblcdb_gpu_snappy.so")
 CORPUS_LIB = os.path.join(PKG, "libcorpus.so")
 # Test-only: the product sources plus the decoders that lost their A/B
-# (lgs_decode_probe.hip, -DLGS_PROBE_DECODERS).  Never loaded by lcdb or the
+# (PROBE_SOURCES, -DLGS_PROBE_DECODERS).  Never loaded by lcdb or the
 # product path; tests/test_gpu_probe_decoders.py runs it in a subprocess.
 PROBE_LIB = os.path.join(PKG, "liblcdb_gpu_snappy_probe.so")
-PROBE_SOURCES = ["lgs_decode_probe.hip", "lgs_decode_group.hip", "lgs_decode_chain.hip"]
+PROBE_SOURCES = ["lgs_decode_probe.hip", "lgs_decode_group.hip", "lgs_decode_chain.hip",
+                 "lgs_decode_ring.hip"]
 
 HIP_SOURCES = ["lgs_api.cpp", "lgs_table_api.cpp", "lgs_encode_service.hip", "lgs_decode.hip",
                "lgs_table.hip", "lgs_bloom.hip", "lgs_table_index.cpp", "lgs_probe.hip",
@@ -38,7 +39,7 @@ HIP_HEADERS = ["lgs_device.h", "lgs_launch.h", "lgs_decode_common.h", "lgs_probe
 EXPORTS_MAP = os.path.join(CSRC, "exports.map")
 # The files that define the two profiled codec kernels and how they are
 # launched (grid, LDS class, split); the host runtime, table and bloom
-# sources do not change what encode_kernel / decode_ring_kernel execute.
+# sources do not change what encode_kernel / decode_pair_kernel execute.
 CODEC_KERNEL_FILES = ["lgs_encode.hip", "lgs_encode_service.hip", "lgs_decode.hip", "lgs_device.h", "lgs_launch.h",
                       "lgs_decode_common.h", "lgs_probe_hooks.h", "lgs_service.h"]
 ARCH = "gfx950"
@@ -110,7 +111,7 @@ def build_hip(force: bool = False, extra: list[str] | None = None, out: str = LI
 
 
 def build_probe(force: bool = False) -> str:
-    """The probe library (tests only): product sources + lgs_decode_probe.hip."""
+    """The probe library (tests only): product sources + PROBE_SOURCES."""
     deps = [os.path.join(CSRC, s) for s in PROBE_SOURCES]
     if force or _stale(PROBE_LIB, deps + [LIB]):
         build_hip(force=True, out=PROBE_LIB,

@@ -927,35 +927,55 @@ int decode_one(uint8_t* zp, const uint8_t* xp, size_t xn, int* ok) {
 }
 
 // Kernel options: lgs_set_option(), initial values from the environment.
+//
+// The values of "decoder" (LGS_DECODE_KERNEL) and "wide" (LGS_WIDE_DECODER),
+// one table each for the environment reader, lgs_set_option and the warning
+// below.  probe_only: a decoder that lost its A/B and exists in the probe
+// library only (build.PROBE_SOURCES); the product rejects its name.
+#ifdef LGS_PROBE_DECODERS
+constexpr bool kProbeLibrary = true;
+#else
+constexpr bool kProbeLibrary = false;
+#endif
+struct OptionValue {
+  const char* name;
+  int value;
+  bool probe_only;
+};
+constexpr OptionValue kDecoderValues[] = {
+    {"", kDecAuto, false},      {"auto", kDecAuto, false},  {"ring", kDecRing, false},
+    {"wave", kDecWave, false},  {"ring32", kDecRing32, true}, {"chain", kDecChain, true},
+    {"group", kDecGroup, true}, {"quad", kDecQuad, true},   {"ops", kDecOps, true}};
+constexpr OptionValue kWideValues[] = {
+    {"", kWideWalk, false}, {"walk", kWideWalk, false}, {"group", kWideGroup, true},
+    {"trips", kWideTrips, true}};
+
+// The entry `name` names (nullptr: none, or no name).
+template <size_t N>
+const OptionValue* option_value(const OptionValue (&table)[N], const char* name) {
+  for (const OptionValue& e : table)
+    if (name && !strcmp(name, e.name)) return &e;
+  return nullptr;
+}
+// Whether this library has the entry's decoder.
+bool option_usable(const OptionValue* e) { return e && (kProbeLibrary || !e->probe_only); }
+
 Options& options_init() {
   static Options* o = [] {
     Options* v = new Options;
     const char* dk = getenv("LGS_DECODE_KERNEL");
-    if (dk && !strcmp(dk, "ring")) v->decoder = kDecRing;
-    if (dk && !strcmp(dk, "ring32")) v->decoder = kDecRing32;
-    if (dk && !strcmp(dk, "wave")) v->decoder = kDecWave;
-#ifdef LGS_PROBE_DECODERS
-    if (dk && !strcmp(dk, "chain")) v->decoder = kDecChain;
-    if (dk && !strcmp(dk, "group")) v->decoder = kDecGroup;
-    const char* wg = getenv("LGS_WIDE_DECODER");
-    if (wg && !strcmp(wg, "group")) v->wide = kWideGroup;
-    if (dk && !strcmp(dk, "quad")) v->decoder = kDecQuad;
-    if (dk && !strcmp(dk, "ops")) v->decoder = kDecOps;
     const char* wd = getenv("LGS_WIDE_DECODER");
-    if (wd && !strcmp(wd, "trips")) v->wide = kWideTrips;
-#endif
-#ifndef LGS_PROBE_DECODERS
-    // The decoders that lost their A/B exist in the probe library only: say
-    // so rather than silently measuring the default.
-    const char* wd0 = getenv("LGS_WIDE_DECODER");
-    if ((dk && (!strcmp(dk, "quad") || !strcmp(dk, "ops") || !strcmp(dk, "group") ||
-                !strcmp(dk, "chain"))) ||
-        (wd0 && (!strcmp(wd0, "trips") || !strcmp(wd0, "group"))))
+    const OptionValue* d = option_value(kDecoderValues, dk);
+    const OptionValue* w = option_value(kWideValues, wd);
+    if (option_usable(d)) v->decoder = d->value;
+    if (option_usable(w)) v->wide = w->value;
+    // A probe-library decoder named to the product: say so rather than
+    // silently measuring the default.
+    if ((d && !option_usable(d)) || (w && !option_usable(w)))
       fprintf(stderr,
               "lcdb_gpu_snappy: LGS_DECODE_KERNEL=%s LGS_WIDE_DECODER=%s names a probe-library "
               "decoder; this library uses its default decoders\n",
-              dk ? dk : "", wd0 ? wd0 : "");
-#endif
+              dk ? dk : "", wd ? wd : "");
     const char* vo = getenv("LGS_VERIFY_OVERLAP");
     if (vo && !strcmp(vo, "0")) v->verify_overlap = 0;
     const char* ns = getenv("LGS_NO_SPLIT");
@@ -1035,19 +1055,9 @@ int lgs_set_option(const char* name, const char* value) {
   if (!name || !value) return fail(LGS_EINVAL, "NULL argument");
   Options& o = options();
   if (!strcmp(name, "decoder")) {
-    if (!strcmp(value, "auto") || !*value) o.decoder = kDecAuto;
-    else if (!strcmp(value, "ring")) o.decoder = kDecRing;
-    else if (!strcmp(value, "ring32")) o.decoder = kDecRing32;
-    else if (!strcmp(value, "wave")) o.decoder = kDecWave;
-#ifdef LGS_PROBE_DECODERS
-    else if (!strcmp(value, "chain")) o.decoder = kDecChain;
-    else if (!strcmp(value, "group")) o.decoder = kDecGroup;
-    // The decoders that lost their A/B exist in the probe library only
-    // (lgs_decode_probe.hip); the product rejects them.
-    else if (!strcmp(value, "quad")) o.decoder = kDecQuad;
-    else if (!strcmp(value, "ops")) o.decoder = kDecOps;
-#endif
-    else return fail(LGS_EINVAL, "decoder '%s' (auto, ring or wave)", value);
+    const OptionValue* e = option_value(kDecoderValues, value);
+    if (!option_usable(e)) return fail(LGS_EINVAL, "decoder '%s' (auto, ring or wave)", value);
+    o.decoder = e->value;
     return LGS_OK;
   }
   if (!strcmp(name, "inject_alloc_failures")) {   // test hook (big_alloc)
@@ -1059,12 +1069,9 @@ int lgs_set_option(const char* name, const char* value) {
     return LGS_OK;
   }
   if (!strcmp(name, "wide")) {
-    if (!strcmp(value, "walk") || !*value) o.wide = kWideWalk;
-#ifdef LGS_PROBE_DECODERS
-    else if (!strcmp(value, "group")) o.wide = kWideGroup;
-    else if (!strcmp(value, "trips")) o.wide = kWideTrips;
-#endif
-    else return fail(LGS_EINVAL, "wide '%s' (walk)", value);
+    const OptionValue* e = option_value(kWideValues, value);
+    if (!option_usable(e)) return fail(LGS_EINVAL, "wide '%s' (walk)", value);
+    o.wide = e->value;
     return LGS_OK;
   }
   if (!strcmp(name, "service")) {   // the drop-in's resident waves (LGS_DROPIN_SERVICE)

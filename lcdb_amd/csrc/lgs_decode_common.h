@@ -1,7 +1,8 @@
 // lgs_decode_common.h -- device helpers shared by the gfx950 decoders
-// (lgs_decode.hip, and the probe-only decoders of lgs_decode_probe.hip):
-// 16-byte global and LDS accesses, byte-exact stores, the output flush of
-// the wave decoders and the tag parse of snappy.c:210-324 with its rejects.
+// (lgs_decode.hip, and the probe-only decoders of lgs_decode_probe.hip and
+// lgs_decode_ring.hip): 16-byte global and LDS accesses, byte-exact stores,
+// the output flush of the wave decoders, the tag parse of snappy.c:210-324
+// with its rejects and the per-lane LDS rings of the lane-per-block decoders.
 #pragma once
 
 #include "lgs_device.h"
@@ -140,7 +141,7 @@ __device__ __forceinline__ void flush_out(gptr<uint8_t> dst, const uint8_t* o, u
 }
 
 // ---------------------------------------------------------------------------
-// Per-lane helpers of the ring decoder below (one lane decodes one block).
+// Per-lane helpers of the lane-per-block decoders (one lane decodes one block).
 // Reads may touch 16 bytes past a block's input (see lgs_decode_batch_dev).
 // (A kernel that moved every byte as a 16-byte global access of its own
 // lane, straight HBM to HBM, ran C2 at 373 GiB/s: its texture addresser was
@@ -244,5 +245,64 @@ __device__ __forceinline__ uint8_t gl_byte(const uint8_t* p) {
 typedef u32x4 u32x4_l1 __attribute__((aligned(1)));
 __device__ __forceinline__ u32x4 lrd16(const uint8_t* p) { return *(const u32x4_l1*)p; }
 __device__ __forceinline__ void lwr16(uint8_t* p, u32x4 v) { *(u32x4_l1*)p = v; }
+
+// ---------------------------------------------------------------------------
+// The per-lane LDS rings of the lane-per-block decoders: decode_pair_kernel
+// (lgs_decode.hip) and, in the probe library, the kernel it replaced
+// (lgs_decode_ring.hip).  Each lane keeps a ring of its compressed stream
+// and a ring of its output, both followed by a mirror of the ring's start so
+// that a read from any ring offset is linear.
+// ---------------------------------------------------------------------------
+namespace ring {
+constexpr uint32_t kInRing = 128, kInStride = 208;     // ring + 64 mirror + 16 sink
+// 16 pad + ring + 64 mirror + 16, + 16 for the ring's shift by the
+// destination's alignment (below).  Still 15 LDS granules per wave.
+constexpr uint32_t kOutRing = 256, kOutStride = 368;
+constexpr uint32_t kNear = 240;                         // ring minus one wild chunk
+constexpr uint32_t kFlush = 128;
+constexpr uint32_t kInSink = kInRing + 64;             // a lane's sink slot (its slack)
+}  // namespace ring
+
+
+// The tag's 5 bytes (parse_tag reads tv.x and the low byte of tv.y) from
+// two aligned dwords: an unaligned ds_read_b128 is replayed (+~60 LDS
+// cycles; the ring's SQ_LDS_UNALIGNED_STALL was 55 % of its LDS-busy
+// cycles on C2, profiles/r5c_pmc.txt).  (The pieces' 16-byte accesses stay
+// ds_read/write_b128: as aligned dwords (5 reads + v_alignbyte, a write as
+// 3 bytes + 4 dwords) they are exact and slower, 339 against 274 us, and
+// even wrong-byte aligned b128s gain only 3 % -- the instructions, not the
+// LDS cycles, are what a trip waits on; profiles/r5d_ab.txt.)
+__device__ __forceinline__ u32x4 rrd_tag(const uint8_t* p) {
+  const uint32_t r = (uint32_t)(uintptr_t)p & 3u;
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(p - r);
+  const uint32_t d0 = w[0], d1 = w[1];
+  return u32x4{__builtin_amdgcn_alignbyte(d1, d0, r), d1 >> (8 * r), 0u, 0u};
+}
+
+// 16 bytes at output offset p of a lane's ring (ob = ring start): the ring
+// copy, plus the mirror copy (r < 64) or the wrapped part (r > 240), which
+// only those lanes write.
+__device__ __forceinline__ void out_put(uint8_t* ob, uint32_t p, u32x4 v) {
+  const uint32_t r = p & (ring::kOutRing - 1);
+  lwr16(ob + r, v);
+  // r < 64 or r > 240 as one unsigned compare; the second copy's offset as
+  // one select (its value for the other lanes is never used).  (Written by
+  // every lane, to a pad for the others, it cost 1.5 %; the whole trip
+  // branch-free that way, 35 %: LDS stores cost by the lanes they move,
+  // profiles/r4h_session.txt.)
+  if (r - 64 > 176u) lwr16(ob + (int32_t)r + (r < 64 ? 256 : -256), v);
+}
+
+// A cooperative job (a refill or a flush) of one lane, 16 bytes: the lane
+// rides in the top byte of the pointer's high word (virtual addresses are
+// 48-bit).
+struct RingJob {
+  uint32_t off, cnt, plo, phil;
+  __device__ RingJob() = default;
+  __device__ RingJob(uint32_t ln, uint32_t o, uint32_t c, uint64_t p)
+      : off(o), cnt(c), plo((uint32_t)p), phil((uint32_t)(p >> 32) | (ln << 24)) {}
+  __device__ uint32_t lane() const { return phil >> 24; }
+  __device__ uint64_t ptr() const { return ((uint64_t)(phil & 0xffffffu) << 32) | plo; }
+};
 
 }  // namespace lgs

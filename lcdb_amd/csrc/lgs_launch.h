@@ -16,7 +16,7 @@ namespace lgs {
 // launch path reads the environment).
 enum DecodeKernel {
   kDecAuto = 0, kDecRing = 1, kDecWave = 2, kDecQuad = 3, kDecOps = 4, kDecGroup = 5, kDecChain = 6,
-  kDecRing32 = 7   // the lane-per-block ring route through decode_ring_kernel<true, 32>
+  kDecRing32 = 7   // probe library: the "ring" route through decode_ring_kernel<true, 32>
 };
 // Outputs over the 16 KiB class: the one-tag walk (default), or, in the
 // probe library, the trip decoder or the workgroup decoder.
@@ -59,14 +59,16 @@ struct EncodeArgs {
 // max_out: largest out_cap in the launch (selects the LDS class).
 hipError_t launch_decode(const DecodeArgs& a, uint32_t max_out, hipStream_t s);
 #ifdef LGS_PROBE_DECODERS
-// Probe library only (lgs_decode_probe.hip): the decoders that lost their
-// A/B, selectable through lgs_set_option for tests and measurements.
+// Probe library only (lgs_decode_probe.hip, lgs_decode_ring.hip): the
+// decoders that lost their A/B, selectable through lgs_set_option for tests
+// and measurements.
 hipError_t launch_decode_quad(const DecodeArgs& a, hipStream_t s);
 hipError_t launch_decode_ops(const DecodeArgs& a, hipStream_t s);
 hipError_t launch_decode_trips(const DecodeArgs& a, hipStream_t s);
+hipError_t launch_decode_ring32(const DecodeArgs& a, hipStream_t s);
 #endif
-// The ring decoder (lane per block, large batches), for the split launch.
-hipError_t launch_decode_ring(const DecodeArgs& a, hipStream_t s);
+// The pair decoder (lane per block, large batches), for the split launch.
+hipError_t launch_decode_pair(const DecodeArgs& a, hipStream_t s);
 
 #ifdef LGS_PROBE_DECODERS
 // Probe library only: the workgroup (pointer-jumping) decoder of

@@ -3,21 +3,32 @@
 // below expands to nothing there; probe builds (tools/mk_variants.sh with
 // -DLGS_PROBE_..., never loaded by lcdb or bench.py) turn one family on.
 //
-//   LGS_PROBE_RING_PHASES  decode_ring_kernel: shader-clock cycles per trip
-//                          phase, summed per wave (tools/ring_phases.py)
-//   LGS_PROBE_TRIPCOUNT    decode_ring_kernel: trips per wave (ring_trips.py)
-//   LGS_PROBE_NOFAR / NOFLUSH  decode_ring_kernel: drop the far-copy loads /
+//   LGS_PROBE_RING_PHASES  decode_pair_kernel: shader-clock cycles per trip
+//                          phase of each role, summed per wave
+//                          (tools/ring_phases.py)
+//   LGS_PROBE_NOFAR / NOFLUSH  decode_pair_kernel: drop the far-copy loads /
 //                          the flush stores (same control flow; traffic
 //                          calibration)
+//   LGS_PROBE_DEC_TIMING   decode_kernel: staging, walk and flush cycles
+//                          (tools/dec_phases.py)
+//   LGS_PROBE_FORCE_REPLAY / ENC_TIMING  encode_kernel (tools/enc_phases.py)
+//
+// decode_ring_kernel, the kernel decode_pair_kernel replaced, is in the probe
+// library only (lgs_decode_ring.hip: a probe build needs -DLGS_PROBE_DECODERS
+// and the probe sources of build.PROBE_SOURCES to run it, selected with
+// "ring32").  It uses the RING_PH stamps and the traffic-calibration hooks
+// below too; the hooks it alone uses (its out_len values under
+// LGS_PROBE_RING_PHASES, and LGS_PROBE_TRIPCOUNT) are defined in its source.
 #pragma once
 
 #include <stdint.h>
 
-// ---- decode_ring_kernel trip phases --------------------------------------
+// ---- trip phases: the stamps (decode_pair_kernel through the LGS_PAIR_PH
+// aliases below, decode_ring_kernel directly) --------------------------------
 // RING_PH_DECL at the kernel's start, RING_PH(k) at the end of phase k
-// (adds the cycles since the previous stamp to phase k), RING_PH_STORE(
-// lane, slot_ok, dst32) at the end: lane k < 8 writes phase k's sum, lane 8
-// the trip count, into its block's out_len entry.
+// (adds the cycles since the previous stamp to phase k), RING_PH_TRIP() once
+// a trip; lgs_ring_ph_value_ is what a lane writes at the end: lane k < 8
+// phase k's sum, lane 8 the trip count.
 #ifdef LGS_PROBE_RING_PHASES
 #define LGS_RING_PH_DECL                                   \
   uint32_t ph_[8] = {0, 0, 0, 0, 0, 0, 0, 0};               \
@@ -30,8 +41,6 @@
     ph_t_ = t_;                                            \
   } while (0)
 #define LGS_RING_PH_TRIP() (++ph_trips_)
-#define LGS_RING_PH_VALUE(lane, dflt) lgs_ring_ph_value_(ph_, ph_trips_, (lane), (dflt))
-#define LGS_RING_PH_ACTIVE 1
 __device__ __forceinline__ uint32_t lgs_ring_ph_value_(const uint32_t* ph, uint32_t trips,
                                                        uint32_t lane, uint32_t dflt) {
   uint32_t v = lane == 8 ? trips : dflt;
@@ -43,8 +52,6 @@ __device__ __forceinline__ uint32_t lgs_ring_ph_value_(const uint32_t* ph, uint3
 #define LGS_RING_PH_DECL do {} while (0)
 #define LGS_RING_PH(k) do {} while (0)
 #define LGS_RING_PH_TRIP() do {} while (0)
-#define LGS_RING_PH_VALUE(lane, dflt) (dflt)
-#define LGS_RING_PH_ACTIVE 0
 #endif
 
 // ---- decode_pair_kernel trip phases (the same probe build) ----------------
@@ -76,17 +83,7 @@ __device__ __forceinline__ uint32_t lgs_ring_ph_value_(const uint32_t* ph, uint3
 #define LGS_PAIR_PH_END_WALKER(ok, lane, ptr) do {} while (0)
 #endif
 
-#ifdef LGS_PROBE_TRIPCOUNT
-#define LGS_RING_TRIPS_DECL uint32_t trips_ = 0
-#define LGS_RING_TRIP() (++trips_)
-#define LGS_RING_OUT_LEN(v) (trips_)
-#else
-#define LGS_RING_TRIPS_DECL do {} while (0)
-#define LGS_RING_TRIP() do {} while (0)
-#define LGS_RING_OUT_LEN(v) (v)
-#endif
-
-// ---- decode_ring_kernel traffic calibration -----------------
+// ---- traffic calibration of the lane-per-block decoders ------
 // LGS_RING_FAR_LD16(p): a far copy's 16-byte load; LGS_RING_FLUSH_ST(g, v, c):
 // a flush job's store of c (<= 16) bytes.
 #ifdef LGS_PROBE_NOFAR

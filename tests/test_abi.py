@@ -124,13 +124,15 @@ def test_product_has_only_the_kept_decoders():
     their kernels nor accepts their options (lgs_set_option needs no GPU)."""
     blob = open(build.LIB, "rb").read()
     for k in (b"decode_quad_kernel", b"tag_scan_kernel", b"op_exec_kernel",
-              b"decode_trips_kernel", b"decode_group_kernel", b"decode_chain_kernel"):
+              b"decode_trips_kernel", b"decode_group_kernel", b"decode_chain_kernel",
+              b"decode_ring_kernel"):
         assert k not in blob, k
-    for k in (b"decode_ring_kernel", b"decode_wide_kernel", b"decode_kernel"):
+    for k in (b"decode_pair_kernel", b"decode_wide_kernel", b"decode_kernel"):
         assert k in blob, k
     lib = _native.lib()
     for name, value in (("decoder", "quad"), ("decoder", "ops"), ("decoder", "group"),
-                        ("decoder", "chain"), ("wide", "trips"), ("wide", "group")):
+                        ("decoder", "chain"), ("decoder", "ring32"), ("wide", "trips"),
+                        ("wide", "group")):
         assert lib.lgs_set_option(name.encode(), value.encode()) == _native.LGS_EINVAL, value
     for name, value in (("decoder", "ring"), ("decoder", "wave"), ("decoder", "auto"),
                         ("wide", "walk")):
@@ -138,6 +140,7 @@ def test_product_has_only_the_kept_decoders():
     probe = open(build.PROBE_LIB, "rb").read()
     assert b"decode_quad_kernel" in probe and b"op_exec_kernel" in probe
     assert b"decode_group_kernel" in probe and b"decode_chain_kernel" in probe
+    assert b"decode_ring_kernel" in probe
 
 
 def test_service_option_and_kernels():

@@ -78,7 +78,9 @@ def main() -> None:
         child(sys.argv[2])
         return
     for spec in sys.argv[1:]:
-        # LIB or LIB@DECODER (LGS_DECODE_KERNEL for that child: ring, quad, wave)
+        # LIB or LIB@DECODER (LGS_DECODE_KERNEL for that child: ring, wave; quad,
+        # ring32 and the other probe-library decoders need a LIB built with
+        # -DLGS_PROBE_DECODERS and the probe sources)
         lib, _, dk = spec.partition("@")
         env = dict(os.environ, **({"LGS_DECODE_KERNEL": dk} if dk else {}))
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", lib],

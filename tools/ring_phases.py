@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""Where a ring-decoder trip's cycles go (decode_ring_kernel on C2), from a
+"""Where a trip's cycles go in the lane-per-block decoders on C2, from a
 probe build with -DLGS_PROBE_RING_PHASES (lgs_probe_hooks.h): each wave sums
-the shader-clock cycles (s_memtime) of its trip phases and lane k < 8 of the
-wave writes phase k's sum into its block's out_len, lane 8 the trip count.
+the shader-clock cycles (s_memtime) of its trip phases.
+
+decode_ring_kernel (probe library only, lgs_decode_ring.hip): lane k < 8 of
+the wave writes phase k's sum into its block's out_len, lane 8 the trip count.
 
 Phases: 0 first-slot piece (before the wait), 1 the trip's vmcnt(0),
 2 far-copy and refill landing, 3 flush jobs, 4 first parse, 5 second slot
@@ -10,11 +12,14 @@ Phases: 0 first-slot piece (before the wait), 1 the trip's vmcnt(0),
 s_memtime whose use waits for every outstanding LDS operation too, so LDS
 latency is charged to the phase whose operations are in flight at its end.
 
-The "ring" route is decode_pair_kernel now: its two roles stamp their own
+The "ring" route is decode_pair_kernel: its two roles stamp their own
 phases (PAIR_MOVER, PAIR_WALKER below), the mover's lanes 0-8 and the
 walker's lanes 16-24 of each 64-block workgroup write them.  With
-LGS_DECODE_KERNEL=ring32 the probe build runs decode_ring_kernel and the
-layout above.
+LGS_DECODE_KERNEL=ring32 a probe build that also has -DLGS_PROBE_DECODERS and
+the probe sources (build.PROBE_SOURCES; tools/mk_variants.sh adds them when
+FLAGS hold -DLGS_PROBE_DECODERS) runs decode_ring_kernel and the layout above;
+a build without them only warns that "ring32" names a probe-library decoder
+and runs the pair kernel.
 
 usage: python tools/ring_phases.py PROBE_SO [PRODUCT_SO]
 Prints one JSON line: per-phase cycles per wave (median over waves), per
@@ -31,7 +36,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["piece1", "wait_vmcnt", "landing", "flush", "parse1", "slot2", "refill_req", "loop_test"]
 # decode_pair_kernel (the "ring" route; LGS_DECODE_KERNEL=ring32 selects the
-# old kernel and the layout above): each role's phases 0-4, and 7 = from its
+# probe library's old kernel and the layout above): each role's phases 0-4, and 7 = from its
 # last stamp through the barrier to the top of the next trip, i.e. mostly the
 # wait for the other role.
 PAIR_MOVER = ["wait_vmcnt", "far_landing", "flush", "slot1", "slot2", "", "", "barrier"]

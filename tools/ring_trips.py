@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
-"""Trips per wave of the ring decoder on C2, from a probe build with
+"""Trips per wave of decode_ring_kernel on C2, from a probe build with
 -DLGS_PROBE_TRIPCOUNT (the kernel writes its wave's trip count to out_len).
 Divides a PMC pass's per-wave instruction counts into per-trip counts.
 
-usage: python tools/ring_trips.py PROBE_SO
+The kernel is in the probe library only (lgs_decode_ring.hip), so the build
+also needs -DLGS_PROBE_DECODERS and the probe sources (build.PROBE_SOURCES;
+tools/mk_variants.sh adds them when FLAGS hold -DLGS_PROBE_DECODERS), and the
+run LGS_DECODE_KERNEL=ring32: the default route is decode_pair_kernel, which
+has no trip-count hook.
+
+usage: LGS_DECODE_KERNEL=ring32 python tools/ring_trips.py PROBE_SO
 """
 from __future__ import annotations
 
