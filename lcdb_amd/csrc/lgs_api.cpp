@@ -1427,6 +1427,17 @@ int lgs_set_device(int device) {
   return LGS_OK;
 }
 
+#ifdef LGS_PROBE_DECODERS
+// Probe library only (not in include/lcdb_gpu_snappy.h): on != 0 makes every
+// chunk the current device's encode kernels take run encode_chunk's second
+// pass too (lgs_probe_hooks.h); tests/test_gpu_encode_round.py.
+int lgs_probe_encode_second_pass(int on) {
+  LGS_HIP(enc_second_pass_batch(on != 0));
+  LGS_HIP(enc_second_pass_service(on != 0));
+  return LGS_OK;
+}
+#endif
+
 const char* lgs_last_error(void) { return t_err; }
 
 const char* lgs_version(void) { return "lcdb_gpu_snappy 0.1 gfx950"; }

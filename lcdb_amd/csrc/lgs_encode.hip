@@ -19,8 +19,8 @@
 //    lane receives the entry the serial loop would read and the table ends as
 //    the serial loop leaves it.  The first matching lane ends the search;
 //    lanes after it store back what they received.  A lane receiving a later
-//    position than its own would mean the order broke: the batch then undoes
-//    its swaps and replays lane by lane (never seen on gfx950).
+//    position than its own would mean the order broke: the chunk is then
+//    encoded again, its batches swapping lane by lane (never seen on gfx950).
 //  * one path per round: the loop is rotated so a batch is its only exit
 //    test, and lane validity is recomputed per batch rather than carried
 //    (a carried bool becomes a lane-mask phi merged with exec on every path).
@@ -39,6 +39,20 @@
 namespace lgs {
 
 __constant__ ProbeTable kProbe = ProbeTable();
+
+#ifdef LGS_PROBE_DECODERS
+// The probe library's switch for encode_chunk's second pass
+// (LGS_ENC_REPLAY, lgs_probe_hooks.h); the batch kernels and the service
+// kernel are compiled apart, so each has its own word and setter.
+static __device__ uint32_t lgs_enc_second_pass = 0;
+#ifdef LGS_ENCODE_SERVICE_ONLY
+hipError_t enc_second_pass_service(uint32_t on) {
+#else
+hipError_t enc_second_pass_batch(uint32_t on) {
+#endif
+  return hipMemcpyToSymbol(HIP_SYMBOL(lgs_enc_second_pass), &on, sizeof(on));
+}
+#endif
 
 // Output slot of one block as a raw buffer: byte offset = SGPR cursor +
 // VGPR lane offset, so stores need no 64-bit address arithmetic, and the
@@ -87,6 +101,7 @@ struct LdsIn {
   __device__ uint32_t litbyte(uint32_t p) const { return x[p]; }
   __device__ bool oow(uint32_t, uint32_t) const { return false; }
   __device__ void ensure(uint32_t) {}
+  __device__ void restart() {}
   __device__ uint64_t g64(uint32_t) const { return 0; }
   __device__ uint32_t g32(uint32_t) const { return 0; }
   __device__ uint32_t gbyte(uint32_t) const { return 0; }
@@ -160,6 +175,12 @@ struct WinIn {
   __device__ void ensure(uint32_t P) {
     const uint32_t want = (P < n ? P : n) + sh;
     while (hu < want) stage();
+  }
+  // Back to the chunk's start (encode_chunk's second pass), staged as the
+  // kernel stages a new chunk.
+  __device__ void restart() {
+    hu = 0;
+    ensure(W / 4);
   }
 };
 
@@ -283,7 +304,7 @@ __device__ __forceinline__ uint32_t emit_copy(const OutSlot& o, uint32_t op, uin
 }
 
 // The recorded ops of one chunk, emitted lane-parallel: lane k holds op k
-// (recA = copy end << 16 | copy start, recB = the copy's source), each op
+// (recA = (copy end + kEndBias) << 16 | copy start, recB = minus its distance), each op
 // being the literal from the previous op's end (lit0 for op 0) to its copy
 // start, then the copy (snappy.c:156, :166).  Every lane sizes its op
 // (snappy.c:53-102), a wave scan places it, then
@@ -296,12 +317,17 @@ __device__ __forceinline__ uint32_t emit_copy(const OutSlot& o, uint32_t op, uin
 //      rare) through emit_copy, one op at a time.
 // Returns the output cursor after the k ops.
 constexpr uint32_t kLongLit = 256;
+// The parse carries the end of the last copy plus this (encode_pass), and
+// records it so.
+constexpr uint32_t kEndBias = kWave - 4;
 
-// r = v in the lanes whose bit of the SGPR mask sel is set (one lane: the
-// op's record slot).  A plain v_cndmask with the mask as its condition; in
-// C++ the per-lane bit of an SGPR mask costs a shift and a compare.
-__device__ __forceinline__ void rec_lane(uint32_t& r, uint32_t v, uint64_t sel) {
-  asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(r) : "v"(v), "s"(sel));
+// Op k's record: a = va and b = vb in lane k (all three wave-uniform).  Two
+// v_writelane with the lane in M0 (gfx9 takes one SGPR a VALU instruction,
+// and the value is one); as a one-hot v_cndmask each word took a v_mov too.
+__device__ __forceinline__ void rec_lane(uint32_t& a, uint32_t& b, uint32_t va, uint32_t vb,
+                                         uint32_t k) {
+  asm("s_mov_b32 m0, %4\n\tv_writelane_b32 %0, %2, m0\n\tv_writelane_b32 %1, %3, m0"
+      : "+v"(a), "+v"(b) : "s"(va), "s"(vb), "s"(k) : "m0");
 }
 template <class IN>
 __device__ __forceinline__ uint32_t flush_ops(const OutSlot& o, uint32_t op, const IN& x,
@@ -309,9 +335,10 @@ __device__ __forceinline__ uint32_t flush_ops(const OutSlot& o, uint32_t op, con
                                               uint32_t lit0) {
   const uint32_t lane = lane_id();
   const bool live = lane < k;
-  // (The copy's end is kept mod 2^16: it is 65 536 when a copy ends a 64 KiB
-  // chunk; the length, at most 65 535, is exact mod 2^16.)
-  const uint32_t base = recA & 0xffffu, clen = ((recA >> 16) - base) & 0xffffu, dist = base - recB;
+  // (The copy's end is recorded with the parse's kEndBias and kept mod 2^16;
+  // the length, at most 65 535, is exact mod 2^16.)
+  const uint32_t base = recA & 0xffffu, clen = ((recA >> 16) - kEndBias - base) & 0xffffu,
+                 dist = 0u - recB;
   const uint32_t pend = (uint32_t)__shfl_up((int)(base + clen), 1);
   const uint32_t lit = lane == 0 ? lit0 : pend;
   const uint32_t LL = live ? base - lit : 0u;
@@ -449,19 +476,24 @@ __device__ __forceinline__ void lds_mskor(uint32_t a, uint32_t mask, uint32_t da
 // for the re-probe that follows a copy (snappy.c:172-186): lane 0 is its A
 // at at - 1, lane 1 its B at at; lanes l >= 2 are search probes k + l - 2 of
 // the literal search (snappy.c:138-143), 62 per batch.  A chunk's first
-// batch and a search's later batches leave lanes 0 and 1 off.  e0: offset of
-// lane l's probe from the search start at + 1 in the batch after a copy; e1:
-// offset of the probe after it (the bound check of snappy.c:143; A and B
+// batch and a search's later batches leave lanes 0 and 1 off.  Offsets count
+// from am = at + kEndBias, which is what the parse carries (encode_pass).
+// e0: offset of lane l's probe in the batch after a copy; e1: offset of the
+// probe after it (the bound check of snappy.c:143, compared signed; A and B
 // always pass it: the batch runs only while at < last); bm: 0xffffff in B's
-// lane (its 64-bit compare, snappy.c:182), else 0.
+// lane (its 64-bit compare, snappy.c:182), else 0; vu: all ones in a lane
+// that may match, 0 in A's lane, which never does; l4: lane + 4, the
+// extension's byte.
 struct PostLanes {
-  uint32_t e0, e1, bm;
+  uint32_t e0, e1, bm, vu, l4;
 };
 constexpr uint32_t kProbesPerBatch = kWave - 2;
 __device__ __forceinline__ PostLanes post_lanes(uint32_t lane) {
   const uint32_t pk = lane >= 2 ? lane - 2 : 0;
-  return PostLanes{lane == 0 ? 0xfffffffeu : (lane == 1 ? 0xffffffffu : probe_off(pk)),
-                   lane < 2 ? 0u : probe_off(pk + 1), lane == 1 ? 0xffffffu : 0u};
+  constexpr uint32_t s0 = 1u - kEndBias;              // the search's start, from am
+  return PostLanes{lane == 0 ? s0 - 2 : (lane == 1 ? s0 - 1 : s0 + probe_off(pk)),
+                   lane < 2 ? s0 : s0 + probe_off(pk + 1), lane == 1 ? 0xffffffu : 0u,
+                   lane == 0 ? 0u : 0xffffffffu, lane + 4};
 }
 // Offset of the last lane's probe in the first batch of a search (WinIn staging).
 constexpr uint32_t kPostLast = probe_off(kProbesPerBatch - 1);
@@ -483,8 +515,8 @@ constexpr uint32_t kPostLast = probe_off(kProbesPerBatch - 1);
 // restores the value it received (its received value is a committed position
 // or an old entry exactly when it is at most the match's position: positions
 // grow with the lane, old entries lie before the batch).  A lane receiving a
-// position later than its own would mean the order assumption broke; then
-// the batch restores the table and replays the swaps one lane at a time.
+// position later than its own would mean the order assumption broke; the
+// chunk is then encoded a second time, the swaps made one lane at a time.
 //
 // The re-probe after a copy (PostLanes) is two ordinary probes to the table
 // swap, which gives the serial order's table semantics (B's candidate is
@@ -505,13 +537,31 @@ constexpr uint32_t kPostLast = probe_off(kProbesPerBatch - 1);
 // has the same lane layout, so B's mask and the lanes that may match need
 // no per-batch state, and validity is computed per batch, not carried.
 // Table addresses come straight from the hash (the image at LDS 0,
-// the table at a constant offset folded into the instruction), and an op is
-// recorded by a one-hot lane mask (rec_lane) instead of v_writelane
-// through M0.
-template <uint32_t TAB, class IN>
-__device__ __forceinline__ uint32_t encode_chunk(IN& x, uint32_t n, uint16_t* tab,
-                                                 const OutSlot& o, uint32_t op0,
-                                                 const PostLanes& pl) {
+// the table at a constant offset folded into the instruction).
+//
+// Round 8: what the round costs is mostly its vector instructions (18 waves
+// share four SIMDs, each wave64 VALU instruction holds one for four cycles;
+// the scalar unit has room: DESIGN 4.1), so work that is the same in every
+// lane stays scalar and the round's VALU count is what is kept down.  An op
+// is recorded with two v_writelane through M0 (the one-hot v_cndmask of
+// round 4 took a v_mov and a v_cndmask per word), the order check is a
+// compare ORed into a scalar mask that encode_chunk looks at once per chunk,
+// and the match test is one compare whose VCC is the branch.
+//
+// One pass over a chunk: encode_chunk's parse, with the batch's table swap
+// done in one atomic (SERIAL = false, the product's path) or lane by lane
+// (SERIAL = true, the second pass).  `broke`: a lane received a later
+// position than its own (SERIAL = false only).
+//
+// The parse keeps am = (end of the last copy) + kEndBias rather than the
+// end: the extension starts from the match lane's p and adds 64 per step
+// and the first difference's index at its exit, nothing else; PostLanes
+// carries the bias in the next batch's positions per lane, and the record
+// packs am as it stands (flush_ops takes the bias off).
+template <uint32_t TAB, class IN, bool SERIAL>
+__device__ __forceinline__ uint32_t encode_pass(IN& x, uint32_t n, uint16_t* tab,
+                                                const OutSlot& o, uint32_t op0,
+                                                const PostLanes& pl, bool& broke) {
   const uint32_t lane = lane_id();
   const uint32_t last = n - kMargin;                  // snappy.c:106
 
@@ -532,11 +582,12 @@ __device__ __forceinline__ uint32_t encode_chunk(IN& x, uint32_t n, uint16_t* ta
   constexpr uint32_t kSinkOff = 2 * kSink;            // the sink dword, from the table
 
   uint32_t op = op0;     // output cursor (byte offset in the slot)
-  uint32_t at = 0;       // end of the last copy (snappy.c:167 "emit")
-  uint32_t start = 1;    // first probe position of the current search (snappy.c:112)
+  uint32_t am = kEndBias; // end of the last copy (snappy.c:167 "emit") + kEndBias;
+                          // the search starts one after it (snappy.c:112: 1)
   uint32_t kb = 0;       // the search's probe index in lane 2 of the batch
   uint32_t recA = 0, recB = 0, lit0 = 0;
-  uint64_t sel = 1;      // one-hot: the lane that records the next op
+  uint32_t kop = 0;      // ops recorded: the lane that records the next op
+  uint64_t bad = 0;      // lanes that ever received a later position than their own
 
   // The batch in flight: each lane's probe position, the lanes that are
   // probes (vmask), and the read of bytes p .. p+7 (issued when the batch
@@ -544,8 +595,9 @@ __device__ __forceinline__ uint32_t encode_chunk(IN& x, uint32_t n, uint16_t* ta
   uint32_t p;
   uint64_t vmask = 0;
   Raw64 xr;
-  // The batch's table state, kept for the copy that follows a match.
-  uint32_t prev = 0, h2 = 0, ta = 0, sh = 0, mask = 0;
+  // The batch's table state, kept for the copy that follows a match: what
+  // each lane received and its entry's address.
+  uint32_t prev = 0, h2 = 0, ta = 0;
   // ---- one batch: snappy.c:146-152 for its 64 probes, `valid` the lanes
   // that are probes.  Returns the lanes that match.  (Validity is passed in,
   // not kept: a bool carried around the loop becomes a lane-mask phi merged
@@ -563,50 +615,69 @@ __device__ __forceinline__ uint32_t encode_chunk(IN& x, uint32_t n, uint16_t* ta
     }
     h2 = (xv * kHashMul) >> hsh;                                  // snappy.c:44-47
     ta = valid ? (h2 & ~3u) : kSinkOff;
-    sh = (h2 << 3) & 16u;
-    mask = 0xffffu << sh;
-    const uint32_t old = lds_mskor_rtn<TAB>(ta, mask, p << sh);   // snappy.c:146-148
-    prev = (old >> sh) & 0xffffu;
-    Raw32 yr = x.raw32(prev);                                     // the candidate's bytes
-    // (Checked under the read's latency; the rare path reads them again.)
-    // (A probe build takes this path on every batch, lgs_probe_hooks.h.)
-    if (LGS_ENC_REPLAY(prev > p, vmask)) {
-      // Not in lane order (never seen on gfx950): put back each touched
-      // slot's entry as the batch found it (the one lane per slot that
-      // received a value from before the batch), then swap lane by lane.
-      const uint32_t p0 = lane_val(p, (uint32_t)__builtin_ctzll(vmask));
-      lds_mskor<TAB>(prev < p0 ? ta : kSinkOff, mask, prev << sh);
+    const uint32_t sh = (h2 << 3) & 16u;
+    const uint32_t mask = 0xffffu << sh;
+    if constexpr (SERIAL) {
+      // The second pass: the same swaps, one lane per atomic in lane order,
+      // so each lane receives what the serial loop reads whatever order the
+      // hardware gives the lanes of one instruction.
+      prev = 0;
       for (uint64_t r = vmask; r; r &= r - 1) {
         const uint32_t l = (uint32_t)__builtin_ctzll(r);
         const uint32_t got = lds_mskor_rtn<TAB>(lane == l ? ta : kSinkOff, mask, p << sh);
         prev = lane == l ? (got >> sh) & 0xffffu : prev;
       }
-      yr = x.raw32(prev);
+    } else {
+      const uint32_t old = lds_mskor_rtn<TAB>(ta, mask, p << sh); // snappy.c:146-148
+      // (vec: the candidate's address is formed from prev, one v_bfe for both.)
+      prev = vec((old >> sh) & 0xffffu);
     }
+    // The candidate's bytes are read straight from what the atomic returned.
+    // Whether the lanes were applied in lane order (no lane received a later
+    // position than its own) is not tested here: the lanes only note it in
+    // `bad`, and encode_chunk looks once per chunk.  That is exact.  If the
+    // order broke, a lane was handed some other position of the chunk as its
+    // candidate instead of the serial loop's; it is still a position a lane
+    // wrote, so the read stays inside the chunk, the 4-byte compare is still
+    // made, and whatever it accepts is recorded as a copy of >= 4 bytes.  The
+    // pass then emits a well-formed stream that differs from the reference's
+    // but keeps inside its slot's bound (the buffer descriptor drops anything
+    // beyond), and the second pass writes the right one over it from op0.
+    const Raw32 yr = x.raw32(prev);
+    // Under the read's latency: the order note, and one word per lane that
+    // keeps lane A and the lanes that are no probes from matching (~pl.vu,
+    // all ones where the lane is no probe) next to B's upper bytes
+    // (snappy.c:182: lcdb's 64-bit compare, bytes at..at+6 against a
+    // zero-extended 4-byte load), so the test is one compare straight into a
+    // branch.
+    if constexpr (!SERIAL) bad |= ballot(prev > p) & vmask;
+    // (vec: one v_bitop3 here, so that one more after the read is the test.)
+    const uint32_t w = vec((xh & pl.bm) | ~(valid ? pl.vu : 0u));
     uint32_t yv = yr.value();
     if constexpr (IN::kWin) {
       const bool o4 = valid & x.oow(prev, 4);
       if (ballot(o4)) yv = o4 ? x.g32(prev) : yv;
     }
-    // snappy.c:152; lane B: lcdb's 64-bit compare (snappy.c:182), bytes
-    // at..at+6 against a zero-extended 4-byte load; A never matches.
-    return ballot(((xv ^ yv) | (xh & pl.bm)) == 0) & vmask & ~1ull;
+    return ballot(((xv ^ yv) | w) == 0);                          // snappy.c:152
   };
+  // A probe is on while the probe after it is inside the limit (snappy.c:143):
+  // in the batch after a copy, as a bound on the lane's own position.
+  const uint32_t lim = last - (pl.e1 - pl.e0);
   // A chunk's first batch: the post-copy layout from start = 1, A and B off.
-  bool evalid = (lane >= 2) & (pl.e1 <= last - 1);
-  p = evalid ? 1 + pl.e0 : 0;
+  bool evalid = (lane >= 2) & ((int32_t)(last - am) >= (int32_t)pl.e1);
+  p = evalid ? am + pl.e0 : 0;
   if constexpr (IN::kWin) x.ensure(1 + kPostLast + 16);
   xr = x.raw64(p);
   for (;;) {
-    const uint32_t at_in = at;
+    const uint32_t am_in = am;
     // Rotated: the batch is the loop's last step, so its match test is the
     // loop's only exit (a test in the middle became a selector variable).
     for (uint64_t mm = batch(evalid); mm;
-         mm = batch((int32_t)(last - start) >= (int32_t)pl.e1)) {
+         mm = batch((int32_t)p <= (int32_t)lim)) {
       // ---- the copy (snappy.c:156-169)
       const uint32_t m = (uint32_t)__builtin_ctzll(mm);           // the matching probe
       const uint32_t base = lane_val(p, m);
-      const uint32_t ref = lane_val(prev, m);
+      const uint32_t ndm = lane_val(prev, m) - base;
       // The probes after it did not happen: in each slot they touched, the
       // first of them puts back what it received.  A plain u16 store: the
       // lanes with nothing to put back all aim at the sink, and same-address
@@ -618,56 +689,51 @@ __device__ __forceinline__ uint32_t encode_chunk(IN& x, uint32_t n, uint16_t* ta
       *reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(tab) +
                                    (((lane > m) & (prev <= base)) ? (ta | (h2 & 2u)) : kSinkOff)) =
           (uint16_t)prev;
-      const uint32_t dist = base - ref;
-      uint32_t at_n = base + 4;
+      // 64 bytes per step from a = base, lane l at q = a + 4 + l.  The
+      // step's 64 is added whether it ends the copy or not, so the exit adds
+      // only the first differing lane's index: the copy's end + kEndBias.
+      // (vec: q is formed once a step, for the reads and the bound alike.)
+      uint32_t a = base;
+      uint64_t diff;
 #pragma clang loop unroll(disable)
-      for (;;) {                                                  // snappy.c:163-164
-        const uint32_t q = at_n + lane;
-        if constexpr (IN::kWin) x.ensure(at_n + kWave);
-        // Unconditional reads, unclamped: lanes at q >= n read at most 63
-        // bytes past the chunk (the LDS image has that slack; the window
-        // ring masks its index), and count as a mismatch.
-        uint32_t bq = x.byte(q), br = x.byte(q - dist);
+      do {                                                        // snappy.c:163-164
+        const uint32_t q = vec(a + pl.l4);
+        if constexpr (IN::kWin) x.ensure(a + 4 + kWave);
+        uint32_t bq = x.byte(q), br = x.byte(q + ndm);
         if constexpr (IN::kWin) {
-          const bool orq = x.oow(q - dist, 1) || x.oow(q, 1);
+          const bool orq = x.oow(q + ndm, 1) || x.oow(q, 1);
           if (ballot(orq)) {
-            br = orq ? x.gbyte(q - dist) : br;
+            br = orq ? x.gbyte(q + ndm) : br;
             bq = orq ? x.gbyte(q) : bq;
           }
         }
-        const uint64_t diff = ballot(br != bq) | ballot(q >= n);
-        if (diff) {
-          at_n += (uint32_t)__builtin_ctzll(diff);
-          break;
-        }
-        at_n += kWave;
-      }
+        diff = ballot(br != bq) | ballot(q >= n);
+        a += kWave;
+      } while (!diff);
+      am = a + (uint32_t)__builtin_ctzll(diff);
       // The batch after the copy (snappy.c:172-186 + the next search): its
       // read goes out now, under the op's bookkeeping.  Past the limit
       // (snappy.c:169) no lane of it is on, so it finds no match and ends the
       // chunk.
-      start = at_n + 1;
-      p = start + pl.e0;
-      if constexpr (IN::kWin) x.ensure(start + kPostLast + 16);
+      p = am + pl.e0;
+      if constexpr (IN::kWin) x.ensure(am - kEndBias + 1 + kPostLast + 16);
       xr = x.raw64(p);
       // snappy.c:156 + 166: the literal before the copy (empty after a
       // re-match), then the copy -- recorded, emitted by flush_ops.
-      at = at_n;
-      rec_lane(recA, base | (at_n << 16), sel);
-      rec_lane(recB, ref, sel);
-      sel <<= 1;
-      if (!sel) {                                                 // every 64 ops
+      rec_lane(recA, recB, base | (am << 16), ndm, kop);
+      if (++kop == kWave) {                                       // every 64 ops
         op = flush_ops(o, op, x, recA, recB, kWave, lit0);
-        sel = 1;
-        lit0 = at_n;
+        kop = 0;
+        lit0 = am - kEndBias;
       }
     }
-    if (at >= last) break;
+    if (am - kEndBias >= last) break;
     // No match in the batch: the search ends if a probe of the batch was
     // past the limit (snappy.c:143), else continues with its next 62 probes,
     // from the probe table.
     if ((vmask | 3ull) != ~0ull) break;
-    kb = (at != at_in ? 0u : kb) + kProbesPerBatch;
+    kb = (am != am_in ? 0u : kb) + kProbesPerBatch;
+    const uint32_t start = am - kEndBias + 1;
     const uint32_t kk = kb + lane - 2;
     const bool in_tab = (lane >= 2) & (kk < kProbeTab);
     const uint32_t kc = in_tab ? kk : 0u;
@@ -682,11 +748,29 @@ __device__ __forceinline__ uint32_t encode_chunk(IN& x, uint32_t n, uint16_t* ta
     if constexpr (IN::kWin) x.ensure(start + lane_val(o0, kWave - 1) + 16);
     xr = x.raw64(p);
   }
-  const uint32_t nops = (uint32_t)__builtin_ctzll(sel);
-  if (nops) op = flush_ops(o, op, x, recA, recB, nops, lit0);
+  if (kop) op = flush_ops(o, op, x, recA, recB, kop, lit0);
 
+  broke = bad != 0;
+  const uint32_t at = am - kEndBias;
   if (at < n) op += emit_literal(o, op, x, at, n - at);           // snappy.c:190-192
   return op;
+}
+
+template <uint32_t TAB, class IN>
+__device__ __forceinline__ uint32_t encode_chunk(IN& x, uint32_t n, uint16_t* tab,
+                                                 const OutSlot& o, uint32_t op0,
+                                                 const PostLanes& pl) {
+  bool broke;
+  const uint32_t op = encode_pass<TAB, IN, false>(x, n, tab, o, op0, pl, broke);
+  // The order check, once per chunk (never seen to fire on gfx950).
+  // (A probe build takes the second pass on every chunk, or on request:
+  // lgs_probe_hooks.h.)
+  if (!LGS_ENC_REPLAY(broke)) return op;
+  // The first pass's stores land before the second's to the same bytes.
+  __builtin_amdgcn_s_waitcnt(0x0f70);                             // vmcnt(0)
+  order();
+  x.restart();
+  return encode_pass<TAB, IN, true>(x, n, tab, o, op0, pl, broke);
 }
 
 // varint32 header hv (coding.h:140-167) at the slot's start, unless hv is

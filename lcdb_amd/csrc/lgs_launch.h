@@ -82,6 +82,12 @@ hipError_t launch_decode_chain(const DecodeArgs& a, uint32_t max_out, hipStream_
 #endif
 // max_in: largest item length in the launch (<= 65536).
 hipError_t launch_encode(const EncodeArgs& a, uint32_t max_in, hipStream_t s);
+#ifdef LGS_PROBE_DECODERS
+// Probe library only: the switch for encode_chunk's second pass
+// (lgs_probe_hooks.h), one word per compilation of lgs_encode.hip.
+hipError_t enc_second_pass_batch(uint32_t on);
+hipError_t enc_second_pass_service(uint32_t on);
+#endif
 // Sort a mixed-size batch into size classes on the device: class c holds
 // the items with len in (b[c-1], b[c]] (b[3] = infinity); list[c * n + k]
 // is its k-th item (in no particular order), cnt[c] its size.  cnt must be

@@ -135,15 +135,24 @@ __device__ __forceinline__ uint32_t lgs_ring_ph_value_(const uint32_t* ph, uint3
 #endif
 
 // ---- encode_kernel ----------------------------------------------------------
-// LGS_PROBE_FORCE_REPLAY: every search batch takes the lane-by-lane replay
-// path (checked exact on C2), LGS_ENC_REPLAY(cond, vmask) its condition.
+// LGS_ENC_REPLAY(broke): whether encode_chunk runs its second pass (the
+// chunk again from its start, every batch swapping lane by lane); `broke`
+// is the product's condition, a lane that received a later position than
+// its own.  LGS_PROBE_FORCE_REPLAY: every chunk takes the second pass.  The
+// probe library (LGS_PROBE_DECODERS) takes it on request: a device word
+// lgs_enc_second_pass, one per compilation of lgs_encode.hip, set through
+// the library's lgs_probe_encode_second_pass() (tests/
+// test_gpu_encode_round.py).  The product has neither, so its condition is
+// `broke` alone.
 // LGS_PROBE_ENC_TIMING: shader-clock cycles of staging and the parse, stored
 // by lane 0 in the last 16 bytes of the block's output slot
 // (tools/enc_phases.py).
-#ifdef LGS_PROBE_FORCE_REPLAY
-#define LGS_ENC_REPLAY(cond, vmask) (vmask)
+#if defined(LGS_PROBE_FORCE_REPLAY)
+#define LGS_ENC_REPLAY(broke) ((void)(broke), true)
+#elif defined(LGS_PROBE_DECODERS)
+#define LGS_ENC_REPLAY(broke) ((broke) | (__builtin_amdgcn_readfirstlane(lgs_enc_second_pass) != 0))
 #else
-#define LGS_ENC_REPLAY(cond, vmask) (ballot(cond) & (vmask))
+#define LGS_ENC_REPLAY(broke) (broke)
 #endif
 #ifdef LGS_PROBE_ENC_TIMING
 #define LGS_ENC_PH_DECL                                                   \
