@@ -390,6 +390,54 @@ int lgs_table_build_host(const uint8_t *keys, const uint64_t *key_off, const uin
                          int compression, int bits_per_key, int internal_keys, uint8_t *file,
                          size_t file_cap, size_t *file_size);
 
+/* The same build with the entries in device memory and the images left there,
+   cut into the files a compaction writes (db_impl.c:1399-1425): after every
+   ldb_tablegen_add the output file is closed once ldb_tablegen_size reaches
+   max_file_size.  That size moves only when a block is flushed
+   (table_builder.c:251-254, :384-386), so a file ends directly after a block
+   flush: the files' data blocks are the blocks of one continuous cut over all
+   entries, a file that starts at block s ends after the first block whose
+   framed end lies max_file_size or more past the start of s, and per file
+   only the handle offsets (from the file's start), the index key of the last
+   block (the comparator's short successor, :332-341), the filter block, the
+   metaindex, the index block and the footer are the file's own.
+   max_file_size = UINT64_MAX gives one file, the image of
+   lgs_table_build_host; max_file_size = 0 would close a file after every
+   entry with a block pending, which is no block boundary: LGS_EINVAL.
+
+   Entries: the layout lgs_merge_emit_dev and lgs_block_entries_emit_dev write
+   (lgs_block_cut_dev's limits and contract); key_bytes and value_bytes are
+   the totals of the keys and values.  File f is the d_file_size[f] bytes at
+   d_files + d_file_off[f] (starts 16-aligned, the images complete .ldb files
+   byte for byte as lcdb writes them) and holds entries [d_file_first[f],
+   d_file_first[f + 1]).  d_file_off and d_file_size have files_cap_count
+   entries, d_file_first files_cap_count + 1; *n_files and *files_bytes (the
+   end of the last image's room in d_files) are host outputs.
+   lgs_tables_build_bound(...) always suffices for files_cap and sets
+   *max_files to a files_cap_count that does.  LGS_ENOSPC when files_cap or
+   files_cap_count is too small, with *n_files and *files_bytes set to what
+   this call needs and nothing written to the d_file arrays.  n = 0 gives no
+   file (*n_files = 0, LGS_OK): compaction opens no output without a kept
+   entry; this differs on purpose from lgs_table_build_host, whose n = 0 is
+   lcdb's empty table.  Other bad arguments as lgs_table_build_host.
+
+   Scratch comes from a pooled context.  The call synchronises `stream` (for
+   the block count, the file count, one row of counts per file, and once per
+   file for its index and filter block sizes) and has drained it when it
+   returns; no entry, block or image byte crosses the link, only those counts
+   and each file's host-assembled metaindex block. */
+size_t lgs_tables_build_bound(uint32_t n, uint64_t key_bytes, uint64_t value_bytes,
+                              int bits_per_key, uint64_t max_file_size, uint32_t *max_files);
+int lgs_tables_build_dev(const uint8_t *d_keys, const uint64_t *d_key_off,
+                         const uint32_t *d_key_len, const uint8_t *d_vals,
+                         const uint64_t *d_val_off, const uint32_t *d_val_len, uint32_t n,
+                         uint64_t key_bytes, uint64_t value_bytes, uint64_t block_size,
+                         uint32_t restart_interval, int compression, int bits_per_key,
+                         int internal_keys, uint64_t max_file_size, uint8_t *d_files,
+                         size_t files_cap, uint64_t *d_file_off, uint64_t *d_file_size,
+                         uint32_t *d_file_first, uint32_t files_cap_count, uint32_t *n_files,
+                         uint64_t *files_bytes, void *stream);
+
 /* ---- batched point lookups ----
  *
  * ldb_blockiter_create + one ldb_blockiter_seek on the fresh iterator

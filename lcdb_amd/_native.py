@@ -77,6 +77,13 @@ _SIGS = {
     "lgs_table_build_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64,
                                        C.c_uint32, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t,
                                        C.POINTER(C.c_size_t)]),
+    "lgs_tables_build_bound": (C.c_size_t, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_int,
+                                            C.c_uint64, C.POINTER(C.c_uint32)]),
+    "lgs_tables_build_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64,
+                                       C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_int,
+                                       C.c_int, C.c_uint64, _vp, C.c_size_t, _vp, _vp, _vp,
+                                       C.c_uint32, C.POINTER(C.c_uint32),
+                                       C.POINTER(C.c_uint64), _vp]),
     "lgs_block_seek_scratch": (C.c_size_t, [C.c_uint32]),
     "lgs_block_seek_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32,
                                      C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -41,13 +41,47 @@ hipError_t launch_block_emit(const BlockIn& in, uint32_t restart_interval, uint3
                              uint32_t nblocks, const BlockScratch& w, const uint32_t* block_first,
                              const uint64_t* raw_off, const uint32_t* raw_len, uint8_t* raw,
                              const uint64_t* ikey_off, uint8_t* ikey, hipStream_t s);
+// The index keys alone, from icut as the cut (or launch_file_plan) left it.
+hipError_t launch_block_ikeys(const BlockIn& in, uint32_t trim, uint32_t nblocks,
+                              const BlockScratch& w, const uint32_t* block_first,
+                              const uint64_t* ikey_off, uint8_t* ikey, hipStream_t s);
 // The index block's entries (table_builder.c:229-239): value b =
-// ldb_handle_export(hoff[b], hsize[b]) at val + 20 b (format.c:45-63), its
-// offset and length, and key b's length from the index-key offsets.
+// ldb_handle_export(hoff[b] - fstart[b], hsize[b]) at val + 20 b
+// (format.c:45-63), its offset and length, and key b's length from the
+// index-key offsets.  fstart: the start of block b's file in the framed
+// stream (null: 0, one file).
 hipError_t launch_handle_values(const uint64_t* hoff, const uint64_t* hsize,
-                                const uint64_t* ikey_off, uint32_t nblocks, uint8_t* val,
-                                uint64_t* val_off, uint32_t* val_len, uint32_t* key_len,
-                                hipStream_t s);
+                                const uint64_t* fstart, const uint64_t* ikey_off,
+                                uint32_t nblocks, uint8_t* val, uint64_t* val_off,
+                                uint32_t* val_len, uint32_t* key_len, hipStream_t s);
+
+// Compaction's output files over one framed stream of nb blocks (handles
+// hoff / hsize): a file ends after the first block whose framed end lies
+// max_size or more past the file's start (db_impl.c:1417-1425).  next, ja,
+// jb, mark, fof, flen (u32) and fid, fstart, rel (u64): nb + 1 each, scratch
+// of the search and the doubling and per block its file, that file's start,
+// its own offset from there and its framed length; per file (nb + 2 each,
+// entry [files] the end): file_block, file_entry (u32), file_start, file_ikey
+// (u64); count[0] = files.
+struct FilePlan {
+  uint32_t* next; uint32_t* ja; uint32_t* jb; uint32_t* mark; uint64_t* fid;
+  uint32_t* fof; uint64_t* fstart; uint64_t* rel; uint32_t* flen;
+  uint32_t* file_block; uint32_t* file_entry; uint64_t* file_start; uint64_t* file_ikey;
+  uint64_t* count;
+};
+// The plan, after the blocks are framed and before the index keys are
+// emitted: it also turns the index key of every file's last block into the
+// short successor (icut, ilen in w) and rescans cut.ikey_off / counts[3].
+hipError_t launch_file_plan(const BlockIn& in, uint32_t trim, uint32_t nb, const uint64_t* hoff,
+                            const uint64_t* hsize, uint64_t max_size, const BlockScratch& w,
+                            const BlockCut& cut, const FilePlan& p, hipStream_t s);
+// dst_off[b] = file_off[file of b] + block b's offset in its file.
+hipError_t launch_file_place(const FilePlan& p, const uint64_t* file_off, uint64_t* dst_off,
+                             uint32_t nb, hipStream_t s);
+// The 48-byte footer (format.c:92-106) of handles {hoff, hsize}[0] (metaindex)
+// and [1] (index) at image + *end; *file_size = *end + 48.
+hipError_t launch_footer(const uint64_t* hoff, const uint64_t* hsize, const uint64_t* end,
+                         uint8_t* image, uint64_t* file_size, hipStream_t s);
 
 // out = {first[0], (uint32_t)*total}: the encoded lengths of the table's last
 // two blocks (the metaindex block's own, the index block's packed chunks).

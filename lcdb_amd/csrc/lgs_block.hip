@@ -20,6 +20,9 @@
 // and the entries at restart points write the restart array.
 // The index keys are the comparator's shortest separator / short successor
 // (comparator.c:44-88; dbformat.c:232-285 for internal keys).
+// Compaction's output files (tools/sim_table_split.py) are
+// steps 3 and 4 again over the framed blocks: a file ends after the first
+// block that takes it to max_output_file_size (db_impl.c:1417-1425).
 #include "lgs_block.h"
 #include "lgs_device.h"
 
@@ -278,15 +281,16 @@ __global__ __launch_bounds__(256) void ikey_kernel(
 
 __global__ __launch_bounds__(256) void handle_values_kernel(
     const uint64_t* __restrict__ hoff, const uint64_t* __restrict__ hsize,
-    const uint64_t* __restrict__ ikey_off, uint32_t nblocks, uint8_t* __restrict__ val,
-    uint64_t* __restrict__ val_off, uint32_t* __restrict__ val_len,
+    const uint64_t* __restrict__ fstart, const uint64_t* __restrict__ ikey_off, uint32_t nblocks,
+    uint8_t* __restrict__ val, uint64_t* __restrict__ val_off, uint32_t* __restrict__ val_len,
     uint32_t* __restrict__ key_len) {
   const uint32_t b = blockIdx.x * 256 + threadIdx.x;
   if (b >= nblocks) return;
   const gptr<uint8_t> p = to_global(val) + 20ull * b;
+  const uint64_t off = hoff[b] - (fstart ? fstart[b] : 0);   // from its file's start
   uint32_t at = 0;
   for (uint32_t w = 0; w < 2; ++w) {                 // ldb_varint64_write twice, format.c:51-52
-    uint64_t v = w ? hsize[b] : hoff[b];
+    uint64_t v = w ? hsize[b] : off;
     while (v >= 128) {
       p[at++] = (uint8_t)(v | 128);
       v >>= 7;
@@ -302,6 +306,138 @@ __global__ void pair_lens_kernel(const uint32_t* __restrict__ first,
                                  const uint64_t* __restrict__ total, uint32_t* __restrict__ out) {
   out[0] = first[0];
   out[1] = (uint32_t)*total;
+}
+
+// ---- output files --------------------------------------------
+// ldb_tablegen_size moves only with a block flush and compaction compares it
+// after every add (db_impl.c:1417-1425), so a file ends after the first block
+// whose framed end is max_size or more past the file's start: the cut's steps
+// 3 and 4 once more, over blocks.
+
+__device__ __forceinline__ uint64_t framed_end(const uint64_t* __restrict__ hoff,
+                                               const uint64_t* __restrict__ hsize, uint32_t b) {
+  return hoff[b] + hsize[b] + 5;                     // contents, type, crc (table_builder.c:150)
+}
+
+__global__ __launch_bounds__(256) void file_next_kernel(const uint64_t* __restrict__ hoff,
+                                                        const uint64_t* __restrict__ hsize,
+                                                        uint64_t max_size,
+                                                        uint32_t* __restrict__ next,
+                                                        uint32_t* __restrict__ mark, uint32_t nb) {
+  const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+  if (s >= nb) return;
+  const uint64_t start = hoff[s];
+  uint32_t lo = s, hi = nb, probe = s, step = 1;
+  for (;;) {
+    if (framed_end(hoff, hsize, probe) - start >= max_size) {
+      hi = probe;
+      break;
+    }
+    lo = probe + 1;
+    if (lo >= nb) break;
+    probe = nb - 1 - probe > step ? probe + step : nb - 1;
+    if (step < (1u << 30)) step <<= 1;
+  }
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (framed_end(hoff, hsize, mid) - start >= max_size) hi = mid;
+    else lo = mid + 1;
+  }
+  next[s] = lo < nb ? lo + 1 : nb;
+  mark[s] = s == 0 ? 1u : 0u;
+}
+
+// The index key of a file's last block is the short successor of its last
+// key (table_builder.c:332-341), not the separator blocks_kernel chose.
+__global__ __launch_bounds__(256) void file_last_keys_kernel(
+    const uint8_t* __restrict__ keys, const uint64_t* __restrict__ key_off,
+    const uint32_t* __restrict__ key_len, const uint32_t* __restrict__ block_first,
+    const uint32_t* __restrict__ fmark, uint32_t trim, uint32_t* __restrict__ ilen,
+    uint32_t* __restrict__ icut, uint32_t nb) {
+  const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= nb || (b + 1 < nb && !fmark[b + 1])) return;
+  const uint32_t la = block_first[b + 1] - 1, kla = key_len[la], ua = kla - trim;
+  const gptr<const uint8_t> a = to_global(keys) + key_off[la];
+  uint32_t cut = kNoCut;
+  for (uint32_t t = 0; t < ua; ++t)                  // comparator.c:72-88
+    if (a[t] != 0xffu) {
+      cut = t;
+      break;
+    }
+  if (trim && cut != kNoCut && cut + 1 >= ua) cut = kNoCut;   // dbformat.c:267-285
+  icut[b] = cut;
+  ilen[b] = cut == kNoCut ? kla : cut + 1 + trim;
+}
+
+// Per file f (the marked blocks): its first block, first entry, start in the
+// framed stream and first index-key byte; entry [files] of each is the end.
+__global__ __launch_bounds__(256) void file_rows_kernel(
+    const uint32_t* __restrict__ fmark, const uint64_t* __restrict__ fid,
+    const uint32_t* __restrict__ fnext, const uint32_t* __restrict__ block_first,
+    const uint64_t* __restrict__ hoff, const uint64_t* __restrict__ hsize,
+    const uint64_t* __restrict__ ikey_off, uint32_t* __restrict__ file_block,
+    uint32_t* __restrict__ file_entry, uint64_t* __restrict__ file_start,
+    uint64_t* __restrict__ file_ikey, uint32_t nb) {
+  const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= nb || !fmark[b]) return;
+  const uint32_t f = (uint32_t)fid[b];
+  file_block[f] = b;
+  file_entry[f] = block_first[b];
+  file_start[f] = hoff[b];
+  file_ikey[f] = ikey_off[b];
+  if (fnext[b] == nb) {
+    file_block[f + 1] = nb;
+    file_entry[f + 1] = block_first[nb];
+    file_start[f + 1] = framed_end(hoff, hsize, nb - 1);
+    file_ikey[f + 1] = ikey_off[nb];
+  }
+}
+
+// Per block: its file, that file's start, its offset from there, and its
+// framed length.
+__global__ __launch_bounds__(256) void file_blocks_kernel(
+    const uint32_t* __restrict__ fmark, const uint64_t* __restrict__ fid,
+    const uint64_t* __restrict__ file_start, const uint64_t* __restrict__ hoff,
+    const uint64_t* __restrict__ hsize, uint32_t* __restrict__ fof,
+    uint64_t* __restrict__ fstart, uint64_t* __restrict__ rel, uint32_t* __restrict__ flen,
+    uint32_t nb) {
+  const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= nb) return;
+  const uint32_t f = (uint32_t)fid[b] - (fmark[b] ? 0u : 1u);
+  fof[b] = f;
+  fstart[b] = file_start[f];
+  rel[b] = hoff[b] - file_start[f];
+  flen[b] = (uint32_t)hsize[b] + 5u;
+}
+
+// Where block b's framed bytes go: its place in its file, at that file's image.
+__global__ __launch_bounds__(256) void file_place_kernel(
+    const uint32_t* __restrict__ fof, const uint64_t* __restrict__ rel,
+    const uint64_t* __restrict__ file_off, uint64_t* __restrict__ dst_off, uint32_t nb) {
+  const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= nb) return;
+  dst_off[b] = file_off[fof[b]] + rel[b];
+}
+
+// The footer (format.c:92-106) behind the index block, and the file's size.
+__global__ void footer_kernel(const uint64_t* __restrict__ hoff,
+                              const uint64_t* __restrict__ hsize,
+                              const uint64_t* __restrict__ end, uint8_t* __restrict__ image,
+                              uint64_t* __restrict__ file_size) {
+  const gptr<uint8_t> p = to_global(image) + *end;
+  uint32_t at = 0;
+  for (uint32_t w = 0; w < 4; ++w) {                 // metaindex handle, index handle
+    uint64_t v = w & 1 ? hsize[w >> 1] : hoff[w >> 1];
+    while (v >= 128) {
+      p[at++] = (uint8_t)(v | 128);
+      v >>= 7;
+    }
+    p[at++] = (uint8_t)v;
+  }
+  while (at < 40) p[at++] = 0;
+  const uint64_t magic = 0xdb4775248b80fb57ull;      // LDB_TABLE_MAGIC (format.h:26)
+  for (uint32_t i = 0; i < 8; ++i) p[40 + i] = (uint8_t)(magic >> (8 * i));
+  *file_size = *end + 48;
 }
 
 uint32_t grid256(uint32_t n) { return (n + 255) / 256; }
@@ -376,13 +512,69 @@ hipError_t launch_block_emit(const BlockIn& in, uint32_t R, uint32_t trim, uint3
   return hipGetLastError();
 }
 
+hipError_t launch_block_ikeys(const BlockIn& in, uint32_t trim, uint32_t nblocks,
+                              const BlockScratch& w, const uint32_t* block_first,
+                              const uint64_t* ikey_off, uint8_t* ikey, hipStream_t s) {
+  if (in.n == 0 || nblocks == 0) return hipSuccess;
+  const uint32_t per = 256 / kGroup;
+  hipLaunchKernelGGL(ikey_kernel, dim3((nblocks + per - 1) / per), dim3(256), 0, s, in.keys,
+                     in.key_off, in.key_len, block_first, w.icut, ikey_off, ikey, trim, nblocks);
+  return hipGetLastError();
+}
+
 hipError_t launch_handle_values(const uint64_t* hoff, const uint64_t* hsize,
-                                const uint64_t* ikey_off, uint32_t nblocks, uint8_t* val,
-                                uint64_t* val_off, uint32_t* val_len, uint32_t* key_len,
-                                hipStream_t s) {
+                                const uint64_t* fstart, const uint64_t* ikey_off,
+                                uint32_t nblocks, uint8_t* val, uint64_t* val_off,
+                                uint32_t* val_len, uint32_t* key_len, hipStream_t s) {
   if (nblocks == 0) return hipSuccess;
   hipLaunchKernelGGL(handle_values_kernel, dim3(grid256(nblocks)), dim3(256), 0, s, hoff, hsize,
-                     ikey_off, nblocks, val, val_off, val_len, key_len);
+                     fstart, ikey_off, nblocks, val, val_off, val_len, key_len);
+  return hipGetLastError();
+}
+
+hipError_t launch_file_plan(const BlockIn& in, uint32_t trim, uint32_t nb, const uint64_t* hoff,
+                            const uint64_t* hsize, uint64_t max_size, const BlockScratch& w,
+                            const BlockCut& cut, const FilePlan& p, hipStream_t s) {
+  if (nb == 0) return hipSuccess;
+  const dim3 g(grid256(nb)), t(256);
+  hipLaunchKernelGGL(file_next_kernel, g, t, 0, s, hoff, hsize, max_size, p.next, p.mark, nb);
+  // ceil(log2(nb)) rounds reach the nb-th file of a chain of single blocks.
+  const uint32_t* jin = p.next;
+  uint32_t* jout = p.ja;
+  for (uint64_t reach = 1; reach < nb; reach <<= 1) {
+    hipLaunchKernelGGL(jump_kernel, g, t, 0, s, p.mark, jin, jout, nb);
+    jin = jout;
+    jout = jout == p.ja ? p.jb : p.ja;
+  }
+  hipError_t e = launch_scan(2, nullptr, p.mark, w.part, 0, p.fid, p.count, nb, s);
+  if (e != hipSuccess) return e;
+  // The index keys of the files' last blocks, then every key's place again.
+  hipLaunchKernelGGL(file_last_keys_kernel, g, t, 0, s, in.keys, in.key_off, in.key_len,
+                     cut.block_first, p.mark, trim, w.ilen, w.icut, nb);
+  if ((e = launch_scan(2, nullptr, w.ilen, w.part, 0, cut.ikey_off, cut.counts + 3, in.n, s)) !=
+      hipSuccess)
+    return e;
+  hipLaunchKernelGGL(totals_kernel, dim3(1), dim3(1), 0, s, cut.raw_off, cut.ikey_off, cut.counts,
+                     in.n);
+  hipLaunchKernelGGL(file_rows_kernel, g, t, 0, s, p.mark, p.fid, p.next, cut.block_first, hoff,
+                     hsize, cut.ikey_off, p.file_block, p.file_entry, p.file_start, p.file_ikey,
+                     nb);
+  hipLaunchKernelGGL(file_blocks_kernel, g, t, 0, s, p.mark, p.fid, p.file_start, hoff, hsize,
+                     p.fof, p.fstart, p.rel, p.flen, nb);
+  return hipGetLastError();
+}
+
+hipError_t launch_file_place(const FilePlan& p, const uint64_t* file_off, uint64_t* dst_off,
+                             uint32_t nb, hipStream_t s) {
+  if (nb == 0) return hipSuccess;
+  hipLaunchKernelGGL(file_place_kernel, dim3(grid256(nb)), dim3(256), 0, s, p.fof, p.rel, file_off,
+                     dst_off, nb);
+  return hipGetLastError();
+}
+
+hipError_t launch_footer(const uint64_t* hoff, const uint64_t* hsize, const uint64_t* end,
+                         uint8_t* image, uint64_t* file_size, hipStream_t s) {
+  hipLaunchKernelGGL(footer_kernel, dim3(1), dim3(1), 0, s, hoff, hsize, end, image, file_size);
   return hipGetLastError();
 }
 

@@ -942,16 +942,346 @@ int lgs_block_build_host(const uint8_t* keys, const uint64_t* key_off, const uin
   return LGS_OK;
 }
 
-int lgs_table_build_host(const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
-                         const uint8_t* vals, const uint64_t* val_off, const uint32_t* val_len,
-                         uint32_t n, uint64_t block_size, uint32_t restart_interval,
-                         int compression, int bits_per_key, int internal_keys, uint8_t* file,
-                         size_t file_cap, size_t* file_size) {
+// ---- whole tables: lgs_table_build_host and lgs_tables_build_dev ----
+//
+// Both are a data stage (cut, emit, frame: one framed stream of data blocks
+// with their handles) and a tail stage per file (index block, filter block,
+// metaindex, footer); the host call uploads before and downloads after, the
+// device call plans compaction's output files in between.
+
+namespace {
+
+// A table build's part of the arena: the tail's uploads and the small
+// downloads (pinned on the host side), then what lives on the device only.
+struct BuildLayout {
+  uint32_t n = 0, icap = 0;
+  bool filter = false;
+  size_t raw_bound = 0, fbound = 0, ibound = 0, wtotal = 0, bscr = 0, fscr = 0;
+  uint64_t data_bound = 0;
+  size_t o_ftoff = 0, o_ftlen = 0;                                     // the filter block's {offset, length}
+  size_t o_meta = 0, o_toff = 0, o_tlen = 0, o_tencoff = 0, o_titems = 0;   // one upload
+  size_t o_cnt = 0, o_cnt2 = 0, o_end = 0, o_fsize = 0, o_size = 0, o_nfiles = 0, pin_end = 0;
+  CutLayout K, K2;
+  size_t o_raw = 0, o_ikey = 0, o_scr = 0, o_wscr = 0, o_hoff = 0, o_hsize = 0, o_fscr = 0,
+         o_fout = 0, o_hval = 0, o_ivoff = 0, o_ivlen = 0, o_iklen = 0, o_iraw = 0, o_stream = 0,
+         o_thoff = 0, o_thsize = 0, o_tslots = 0, o_tpacked = 0, o_tenclen = 0, o_tenclen2 = 0,
+         o_tpoff = 0, o_tptotal = 0, o_tfoff = 0, o_tpart = 0;
+  // The file plan (lgs_tables_build_dev only).
+  size_t p_next = 0, p_ja = 0, p_jb = 0, p_mark = 0, p_fid = 0, p_fof = 0, p_fstart = 0,
+         p_rel = 0, p_flen = 0, p_fblock = 0, p_fentry = 0, p_fbegin = 0, p_fikey = 0, p_dst = 0;
+
+  // image: the framed stream is followed by one table's tail (the host call);
+  // plan: room for the file plan.
+  int take(Layout& L, uint32_t n_, uint64_t kb, uint64_t vb, int bits_per_key, bool image,
+           bool plan) {
+    n = n_;
+    filter = bits_per_key > 0;
+    raw_bound = lgs_block_build_bound(n, kb, vb);
+    data_bound = raw_bound + (uint64_t)LGS_TRAILER_SIZE * n;
+    if (data_bound >= kMaxDataEnd) return fail(LGS_EINVAL, "table of %llu bytes too large",
+                                               (unsigned long long)data_bound);
+    fbound = filter ? lgs_filter_block_bound(n, n, data_bound, bits_per_key) : 0;
+    ibound = index_block_bound(n, kb);
+    if (fbound > 0x7fffffffull || ibound > 0x7fffffffull)
+      return fail(LGS_EINVAL, "filter or index block over 2^31 bytes");
+    bscr = BlockBuildScratch(n).total;
+    fscr = FilterScratch(data_bound).total;
+    wtotal = WriteScratch(n, raw_bound).total;
+    if (WriteScratch(1, fbound).total > wtotal) wtotal = WriteScratch(1, fbound).total;
+    o_ftoff = L.take(8);
+    o_ftlen = L.take(8);
+    o_meta = L.take(kMetaindexMax + 16);   // tail uploads: metaindex, {offset, length} x 2
+    o_toff = L.take(16);
+    o_tlen = L.take(8);
+    o_tencoff = L.take(16);
+    // The tail's encoder items: the metaindex block and the index block's 64 KiB
+    // chunks ({input offset, output slot} u64, {length, header} u32 each).
+    icap = 2 + (uint32_t)(ibound / kChunk);
+    o_titems = L.take(24 * (size_t)icap);
+    o_cnt = L.take(8 * kBlockCounts);      // downloads
+    o_cnt2 = L.take(8 * kBlockCounts);
+    o_end = L.take(8);
+    o_fsize = L.take(8);
+    o_size = L.take(8);
+    o_nfiles = L.take(8);
+    pin_end = L.at;
+    K.take(L, n);
+    K2.take(L, n);
+    o_raw = L.take(raw_bound);
+    o_ikey = L.take((size_t)kb + 16);
+    o_scr = L.take(bscr);
+    o_wscr = L.take(wtotal);
+    o_hoff = L.take(8 * (size_t)n + 8);
+    o_hsize = L.take(8 * (size_t)n + 8);
+    o_fscr = L.take(fscr);
+    o_fout = L.take(fbound + 16);
+    o_hval = L.take(20 * (size_t)n + 16);
+    o_ivoff = L.take(8 * (size_t)n + 8);
+    o_ivlen = L.take(4 * (size_t)n + 4);
+    o_iklen = L.take(4 * (size_t)n + 4);
+    o_iraw = L.take(ibound + 16);
+    o_stream = L.take((image ? lgs_table_build_bound(n, kb, vb, bits_per_key)
+                             : (size_t)data_bound) + 16);
+    o_thoff = L.take(16);
+    o_thsize = L.take(16);
+    o_tslots = L.take((size_t)icap * chunk_out(kChunk));
+    o_tpacked = L.take(bound_of(ibound) + 64);
+    o_tenclen = L.take(4 * (size_t)icap);
+    o_tenclen2 = L.take(8);
+    o_tpoff = L.take(8 * (size_t)icap);
+    o_tptotal = L.take(8);
+    o_tfoff = L.take(16);
+    o_tpart = L.take(8 * scan_parts(icap) + 16);
+    if (plan) {
+      const size_t m = (size_t)n + 2;
+      p_next = L.take(4 * m);
+      p_ja = L.take(4 * m);
+      p_jb = L.take(4 * m);
+      p_mark = L.take(4 * m);
+      p_fid = L.take(8 * m);
+      p_fof = L.take(4 * m);
+      p_fstart = L.take(8 * m);
+      p_rel = L.take(8 * m);
+      p_flen = L.take(4 * m);
+      p_fblock = L.take(4 * m);
+      p_fentry = L.take(4 * m);
+      p_fbegin = L.take(8 * m);
+      p_fikey = L.take(8 * m);
+      p_dst = L.take(8 * m);
+    }
+    return LGS_OK;
+  }
+  FilePlan plan_at(uint8_t* p) const {
+    return FilePlan{(uint32_t*)(p + p_next), (uint32_t*)(p + p_ja), (uint32_t*)(p + p_jb),
+                    (uint32_t*)(p + p_mark), (uint64_t*)(p + p_fid), (uint32_t*)(p + p_fof),
+                    (uint64_t*)(p + p_fstart), (uint64_t*)(p + p_rel), (uint32_t*)(p + p_flen),
+                    (uint32_t*)(p + p_fblock), (uint32_t*)(p + p_fentry),
+                    (uint64_t*)(p + p_fbegin), (uint64_t*)(p + p_fikey),
+                    (uint64_t*)(p + o_nfiles)};
+  }
+};
+
+struct DataBlocks {
+  uint64_t nb = 0, raw_total = 0, max_raw = 0;
+};
+
+// The data stage: n > 0 entries on the device -> the blocks' cut, their raw
+// bytes, and the framed stream from offset 0 at d + A.o_stream with its
+// handles at d + A.o_hoff / o_hsize and its end in the word d + A.o_end
+// (table_builder.c:215-278).  ikeys: emit the index keys with the blocks (one
+// file: the cut's keys stand).  One synchronisation, for the block count.
+static int build_data(const BuildLayout& A, uint8_t* h, uint8_t* d, hipStream_t s,
+                      const BlockIn& in, uint64_t key_bytes, uint64_t block_size,
+                      uint32_t restart_interval, uint32_t trim, int compression, bool ikeys,
+                      DataBlocks* out) {
+  const BlockBuildScratch B(A.n);
+  const BlockCut cut = A.K.at(d, (uint64_t*)(d + A.o_cnt));
+  LGS_HIP(launch_block_cut(in, block_size, restart_interval, trim, B.at(d + A.o_scr), cut, s));
+  LGS_HIP(hipMemcpyAsync(h + A.o_cnt, d + A.o_cnt, 8 * kBlockCounts, hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipStreamSynchronize(s));
+  const uint64_t* cnt = (const uint64_t*)(h + A.o_cnt);
+  const uint64_t nb = cnt[0], raw_total = cnt[1], max_raw = cnt[2];
+  if (nb == 0 || nb > A.n || raw_total + 16 > A.raw_bound || cnt[3] > key_bytes)
+    return fail(LGS_EINTERNAL, "cut of %u entries: %llu blocks, %llu bytes", A.n,
+                (unsigned long long)nb, (unsigned long long)raw_total);
+  if (max_raw > 0x7fffffffull)
+    return fail(LGS_EINVAL, "a block of %llu bytes: under 2^31 supported",
+                (unsigned long long)max_raw);
+  LGS_HIP(launch_block_emit(in, restart_interval, trim, (uint32_t)nb, B.at(d + A.o_scr),
+                            cut.block_first, cut.raw_off, cut.raw_len, d + A.o_raw, cut.ikey_off,
+                            ikeys ? d + A.o_ikey : nullptr, s));
+  LGS_TRY(table_write(d + A.o_raw, cut.raw_off, cut.raw_len, (uint32_t)nb, (uint32_t)max_raw,
+                      compression, 0, d + A.o_stream, (uint64_t*)(d + A.o_hoff),
+                      (uint64_t*)(d + A.o_hsize), (uint64_t*)(d + A.o_end), d + A.o_wscr,
+                      WriteScratch((uint32_t)nb, raw_total), s));
+  out->nb = nb;
+  out->raw_total = raw_total;
+  out->max_raw = max_raw;
+  return LGS_OK;
+}
+
+// One file of a build: data blocks [b0, b0 + nb) of the cut, whose ne entries
+// start at the cut's block_first[b0]; the data region's bytes are in place at
+// `image`, and the index entries (keys at d + A.o_ikey, handle values at
+// d + A.o_hval) are made.
+struct TailFile {
+  uint32_t b0 = 0, nb = 0, ne = 0;
+  // The data region's length; unknown: the word d + A.o_end holds it, and the
+  // tail synchronises once more to read it.
+  bool len_known = false;
+  uint64_t data_len = 0;
+  const uint64_t* block_off = nullptr;   // device: the nb blocks' offsets in the file
+  uint8_t* image = nullptr;              // device: the file's first byte
+  uint64_t* d_size = nullptr;            // device: receives the file's size
+};
+
+// The tail stage (table_builder.c:280-365): the index block of the file's
+// entries, the filter block of its keys, the metaindex, both framed through
+// the table's compression behind the data region, and the footer.  Counts
+// come back in one synchronisation (two when the data length is not known);
+// what it queues after that is complete on the stream, not on return.  The
+// pinned words it uploads from are rewritten only behind the next
+// synchronisation of this stream, this function's own included.
+static int build_tail(const BuildLayout& A, uint8_t* h, uint8_t* d, hipStream_t s,
+                      const BlockIn& in, int compression, int bits_per_key, int internal_keys,
+                      const TailFile& f) {
+  const BlockBuildScratch B(A.n);
+  const BlockCut cut = A.K.at(d, (uint64_t*)(d + A.o_cnt));
+  const BlockCut cut2 = A.K2.at(d, (uint64_t*)(d + A.o_cnt2));
+  const BlockIn iin{d + A.o_ikey, cut.ikey_off + f.b0, (const uint32_t*)(d + A.o_iklen) + f.b0,
+                    d + A.o_hval, (const uint64_t*)(d + A.o_ivoff) + f.b0,
+                    (const uint32_t*)(d + A.o_ivlen) + f.b0, f.nb};
+  uint64_t data_len = f.data_len, index_len = 0, filter_size = 0;
+  const auto build_filter = [&]() -> int {       // table_builder.c:242-243, :276-277, :292-295
+    LGS_TRY(lgs_filter_block_build_dev(in.keys, in.key_off, in.key_len, f.ne,
+                                       cut.block_first + f.b0, f.block_off, f.nb, data_len,
+                                       bits_per_key, internal_keys, d + A.o_fout, A.fbound,
+                                       (uint64_t*)(d + A.o_fsize), d + A.o_fscr, A.fscr, s));
+    LGS_HIP(hipMemcpyAsync(h + A.o_fsize, d + A.o_fsize, 8, hipMemcpyDeviceToHost, s));
+    return LGS_OK;
+  };
+  if (A.filter && f.len_known) LGS_TRY(build_filter());
+  if (f.nb) {
+    // The index block's entries (:229-239, :332-341): index key -> handle, one
+    // block whatever its size, restart interval 1 (:87).
+    LGS_HIP(launch_block_cut(iin, ~0ull, 1, 0, B.at(d + A.o_scr), cut2, s));
+    LGS_HIP(hipMemcpyAsync(h + A.o_cnt2, d + A.o_cnt2, 8 * kBlockCounts, hipMemcpyDeviceToHost, s));
+    if (!f.len_known)
+      LGS_HIP(hipMemcpyAsync(h + A.o_end, d + A.o_end, 8, hipMemcpyDeviceToHost, s));
+    LGS_HIP(hipStreamSynchronize(s));
+    if (!f.len_known) data_len = *(const uint64_t*)(h + A.o_end);
+    const uint64_t* cnt2 = (const uint64_t*)(h + A.o_cnt2);
+    index_len = cnt2[1];
+    if (data_len > A.data_bound || cnt2[0] != 1 || index_len > A.ibound)
+      return fail(LGS_EINTERNAL, "data blocks end at %llu, index block of %llu bytes",
+                  (unsigned long long)data_len, (unsigned long long)index_len);
+    LGS_HIP(launch_block_emit(iin, 1, 0, 1, B.at(d + A.o_scr), cut2.block_first, cut2.raw_off,
+                              cut2.raw_len, d + A.o_iraw, nullptr, nullptr, s));
+  } else {
+    // An index block with no entries (block_builder.c:68, :143-146).
+    LGS_HIP(hipStreamSynchronize(s));
+    index_len = tail_metaindex(h + A.o_meta, kMetaindexMax, nullptr, 0, 0);
+    LGS_HIP(hipMemcpyAsync(d + A.o_iraw, h + A.o_meta, (size_t)index_len, hipMemcpyHostToDevice, s));
+    LGS_HIP(hipStreamSynchronize(s));
+  }
+  // The filter block (:292-299), stored raw after the data blocks.
+  uint64_t at = data_len;
+  if (A.filter) {
+    if (!f.len_known) {
+      LGS_TRY(build_filter());
+      LGS_HIP(hipStreamSynchronize(s));
+    }
+    filter_size = *(const uint64_t*)(h + A.o_fsize);
+    if (filter_size > A.fbound)
+      return fail(LGS_EINTERNAL, "filter block %llu > bound %zu", (unsigned long long)filter_size,
+                  A.fbound);
+    *(uint64_t*)(h + A.o_ftoff) = 0;
+    *(uint32_t*)(h + A.o_ftlen) = (uint32_t)filter_size;
+    LGS_HIP(hipMemcpyAsync(d + A.o_ftoff, h + A.o_ftoff, 8, hipMemcpyHostToDevice, s));
+    LGS_HIP(hipMemcpyAsync(d + A.o_ftlen, h + A.o_ftlen, 4, hipMemcpyHostToDevice, s));
+    LGS_TRY(table_write(d + A.o_fout, (const uint64_t*)(d + A.o_ftoff),
+                        (const uint32_t*)(d + A.o_ftlen), 1, (uint32_t)filter_size,
+                        LGS_NO_COMPRESSION, at, f.image + at, (uint64_t*)(d + A.o_thoff),
+                        (uint64_t*)(d + A.o_thsize), nullptr, d + A.o_wscr,
+                        WriteScratch(1, filter_size), s));
+    at += filter_size + LGS_TRAILER_SIZE;
+  }
+  // Metaindex (:301-328) and index (:330-344) blocks, both through the
+  // table's compression like every block ldb_tablegen_write_block writes.
+  // The index block grows with the table (C5: 36 MB), and one block is one
+  // wave's work in the encoder, 64 KiB chunk after chunk; the chunks are
+  // independent (snappy.c:370-381), so they are encoded here as items of
+  // their own, as ldb_snappy_encode does, and packed into the block's stream.
+  const size_t meta_len = tail_metaindex(h + A.o_meta, kMetaindexMax,
+                                         A.filter ? kFilterName : nullptr, data_len, filter_size);
+  if (meta_len == 0) return fail(LGS_EINTERNAL, "metaindex block does not fit");
+  const bool snappy = compression == LGS_SNAPPY_COMPRESSION;
+  const uint32_t icap = A.icap;
+  uint64_t* toff = (uint64_t*)(h + A.o_toff);
+  uint32_t* tlen = (uint32_t*)(h + A.o_tlen);
+  uint64_t* tenc_off = (uint64_t*)(h + A.o_tencoff);
+  toff[0] = A.o_meta;          // offsets from the arena's start
+  toff[1] = A.o_iraw;
+  tlen[0] = (uint32_t)meta_len;
+  tlen[1] = (uint32_t)index_len;
+  tenc_off[0] = A.o_tslots;
+  tenc_off[1] = A.o_tpacked;
+  const uint32_t items = 1 + (uint32_t)((index_len + kChunk - 1) / kChunk);
+  if (items > icap) return fail(LGS_EINTERNAL, "index block of %llu bytes",
+                                (unsigned long long)index_len);
+  uint64_t* it_in = (uint64_t*)(h + A.o_titems);
+  uint64_t* it_out = it_in + icap;
+  uint32_t* it_len = (uint32_t*)(it_out + icap);
+  uint32_t* it_hdr = it_len + icap;
+  it_in[0] = A.o_meta;
+  it_len[0] = it_hdr[0] = (uint32_t)meta_len;
+  it_out[0] = A.o_tslots;
+  size_t slot = A.o_tslots + chunk_out((uint32_t)meta_len);
+  for (uint32_t j = 1; j < items; ++j) {
+    const uint64_t off = (uint64_t)(j - 1) * kChunk;
+    it_in[j] = A.o_iraw + off;
+    it_len[j] = (uint32_t)(index_len - off < kChunk ? index_len - off : kChunk);
+    it_hdr[j] = j == 1 ? (uint32_t)index_len : 0xffffffffu;      // snappy.c:368
+    it_out[j] = slot;
+    slot += chunk_out(it_len[j]);
+  }
+  LGS_HIP(hipMemcpyAsync(d + A.o_meta, h + A.o_meta, A.o_cnt - A.o_meta, hipMemcpyHostToDevice, s));
+  uint64_t* part = (uint64_t*)(d + A.o_tpart);
+  uint32_t* enc_len = (uint32_t*)(d + A.o_tenclen);
+  uint32_t* enc_len2 = (uint32_t*)(d + A.o_tenclen2);
+  if (snappy) {
+    const uint64_t* d_out = (const uint64_t*)(d + A.o_titems) + icap;
+    const uint32_t* d_len = (const uint32_t*)(d_out + icap);
+    EncodeArgs ea{d, (const uint64_t*)(d + A.o_titems), d_len, d, d_out, enc_len, d_len + icap,
+                  nullptr, items, nullptr};
+    const uint32_t ichunk = (uint32_t)(index_len < kChunk ? index_len : kChunk);
+    LGS_HIP(launch_encode(ea, meta_len > ichunk ? (uint32_t)meta_len : ichunk, s));
+    LGS_HIP(launch_scan(2, nullptr, enc_len + 1, part, 0, (uint64_t*)(d + A.o_tpoff),
+                        (uint64_t*)(d + A.o_tptotal), items - 1, s));
+    LGS_HIP(launch_pack(d, d_out + 1, enc_len + 1, d + A.o_tpacked,
+                        (const uint64_t*)(d + A.o_tpoff), items - 1, s));
+    LGS_HIP(launch_pair_lens(enc_len, (const uint64_t*)(d + A.o_tptotal), enc_len2, s));
+  }
+  LGS_HIP(launch_scan(1, (const uint32_t*)(d + A.o_tlen), snappy ? enc_len2 : nullptr, part, at,
+                      (uint64_t*)(d + A.o_tfoff), (uint64_t*)(d + A.o_end), 2, s));
+  const FrameArgs fa{d, (const uint64_t*)(d + A.o_toff), (const uint32_t*)(d + A.o_tlen), d,
+                     (const uint64_t*)(d + A.o_tencoff), snappy ? enc_len2 : nullptr,
+                     f.image + at, at, (const uint64_t*)(d + A.o_tfoff),
+                     (uint64_t*)(d + A.o_thoff), (uint64_t*)(d + A.o_thsize), 2};
+  LGS_HIP(launch_frame(fa, s));
+  LGS_HIP(launch_footer((const uint64_t*)(d + A.o_thoff), (const uint64_t*)(d + A.o_thsize),
+                        (const uint64_t*)(d + A.o_end), f.image, f.d_size, s));   // :346-362
+  return LGS_OK;
+}
+
+static int build_args(uint32_t n, uint32_t restart_interval, int compression, int bits_per_key,
+                      int internal_keys) {
   LGS_TRY(block_args(n, restart_interval, internal_keys));
   if (compression != LGS_NO_COMPRESSION && compression != LGS_SNAPPY_COMPRESSION)
     return fail(LGS_EINVAL, "unknown compression type %d", compression);
   if (bits_per_key < 0 || bits_per_key > kMaxBitsPerKey)
     return fail(LGS_EINVAL, "bits_per_key %d out of range", bits_per_key);
+  return LGS_OK;
+}
+
+// What one output file's image may take: its data region and the bounds of
+// its tail's blocks with their trailers, the footer, 16 spare bytes.
+static uint64_t file_slot(uint64_t data_len, uint32_t ne, uint32_t nb, uint64_t ikey_bytes,
+                          int bits_per_key) {
+  const uint64_t filter =
+      bits_per_key > 0 ? lgs_filter_block_bound(ne, nb, data_len, bits_per_key) + LGS_TRAILER_SIZE : 0;
+  return data_len + filter + kMetaindexMax + LGS_TRAILER_SIZE + index_block_bound(nb, ikey_bytes) +
+         LGS_TRAILER_SIZE + kFooterSize + 16;
+}
+
+}  // namespace
+
+int lgs_table_build_host(const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
+                         const uint8_t* vals, const uint64_t* val_off, const uint32_t* val_len,
+                         uint32_t n, uint64_t block_size, uint32_t restart_interval,
+                         int compression, int bits_per_key, int internal_keys, uint8_t* file,
+                         size_t file_cap, size_t* file_size) {
+  LGS_TRY(build_args(n, restart_interval, compression, bits_per_key, internal_keys));
   if (!file || !file_size || (n && (!keys || !key_off || !key_len || !vals || !val_off || !val_len)))
     return fail(LGS_EINVAL, "NULL argument");
   EntryStage E;
@@ -962,227 +1292,173 @@ int lgs_table_build_host(const uint8_t* keys, const uint64_t* key_off, const uin
   Lease lease(batch_pool());
   LGS_TRY(lease.acquire());
   Ctx& c = lease.ctx();
-  const uint32_t trim = internal_keys ? 8u : 0u;
-  const bool filter = bits_per_key > 0;
-  const size_t raw_bound = lgs_block_build_bound(n, E.kb, E.vb);
-  const uint64_t data_bound = raw_bound + (uint64_t)LGS_TRAILER_SIZE * n;
-  if (data_bound >= kMaxDataEnd) return fail(LGS_EINVAL, "table of %llu bytes too large",
-                                             (unsigned long long)data_bound);
-  const size_t fbound = filter ? lgs_filter_block_bound(n, n, data_bound, bits_per_key) : 0;
-  const size_t ibound = index_block_bound(n, E.kb);
-  if (fbound > 0x7fffffffull || ibound > 0x7fffffffull)
-    return fail(LGS_EINVAL, "filter or index block over 2^31 bytes");
   const size_t img_bound = lgs_table_build_bound(n, E.kb, E.vb, bits_per_key);
-  const BlockBuildScratch B(n);
-  const FilterScratch F(data_bound);
-  size_t wtotal = WriteScratch(n, raw_bound).total;
-  if (WriteScratch(1, fbound).total > wtotal) wtotal = WriteScratch(1, fbound).total;
   Layout L;  // uploads | small downloads | device-only
   entries_layout(L, n, &E);
   const size_t up_end = L.at;
-  const size_t o_meta = L.take(kMetaindexMax + 16);   // tail uploads: metaindex, {offset, length} x 2
-  const size_t o_toff = L.take(16);
-  const size_t o_tlen = L.take(8);
-  const size_t o_tencoff = L.take(16);
-  // The tail's encoder items: the metaindex block and the index block's 64 KiB
-  // chunks ({input offset, output slot} u64, {length, header} u32 each).
-  const uint32_t icap = 2 + (uint32_t)(ibound / kChunk);
-  const size_t o_titems = L.take(24 * (size_t)icap);
-  const size_t o_cnt = L.take(8 * kBlockCounts);      // downloads
-  const size_t o_cnt2 = L.take(8 * kBlockCounts);
-  const size_t o_end = L.take(8);
-  const size_t o_fsize = L.take(8);
-  const size_t o_thoff = L.take(16);
-  const size_t o_thsize = L.take(16);
-  const size_t pin_end = L.at;
-  CutLayout K, K2;
-  K.take(L, n);
-  K2.take(L, n);
-  const size_t o_raw = L.take(raw_bound);
-  const size_t o_ikey = L.take((size_t)E.kb + 16);
-  const size_t o_scr = L.take(B.total);
-  const size_t o_wscr = L.take(wtotal);
-  const size_t o_hoff = L.take(8 * (size_t)n + 8);
-  const size_t o_hsize = L.take(8 * (size_t)n + 8);
-  const size_t o_fscr = L.take(F.total);
-  const size_t o_fout = L.take(fbound + 16);
-  const size_t o_hval = L.take(20 * (size_t)n + 16);
-  const size_t o_ivoff = L.take(8 * (size_t)n + 8);
-  const size_t o_ivlen = L.take(4 * (size_t)n + 4);
-  const size_t o_iklen = L.take(4 * (size_t)n + 4);
-  const size_t o_iraw = L.take(ibound + 16);
-  const size_t o_file = L.take(img_bound + 16);
-  const size_t o_tslots = L.take((size_t)icap * chunk_out(kChunk));
-  const size_t o_tpacked = L.take(bound_of(ibound) + 64);
-  const size_t o_tenclen = L.take(4 * (size_t)icap);
-  const size_t o_tenclen2 = L.take(8);
-  const size_t o_tpoff = L.take(8 * (size_t)icap);
-  const size_t o_tptotal = L.take(8);
-  const size_t o_tfoff = L.take(16);
-  const size_t o_tpart = L.take(8 * scan_parts(icap) + 16);
-  LGS_TRY(ctx_reserve(c, L.at, pin_end));
+  BuildLayout A;
+  LGS_TRY(A.take(L, n, E.kb, E.vb, bits_per_key, true, false));
+  LGS_TRY(ctx_reserve(c, L.at, A.pin_end));
   uint8_t* h = c.h_buf;
   uint8_t* d = c.d_buf;
   hipStream_t s = c.stream;
-  uint64_t nb = 0, raw_total = 0, max_raw = 0;
   const BlockIn in = entries_in(d, E, n);
-  const BlockCut cut = K.at(d, (uint64_t*)(d + o_cnt));
+  DataBlocks D;
   if (n) {
     entries_stage(h, E, keys, key_off, key_len, vals, val_off, val_len, n);
     LGS_HIP(hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, s));
-    LGS_HIP(launch_block_cut(in, block_size, restart_interval, trim, B.at(d + o_scr), cut, s));
-    LGS_HIP(hipMemcpyAsync(h + o_cnt, d + o_cnt, 8 * kBlockCounts, hipMemcpyDeviceToHost, s));
-    LGS_HIP(hipStreamSynchronize(s));
-    const uint64_t* cnt = (const uint64_t*)(h + o_cnt);
-    nb = cnt[0], raw_total = cnt[1], max_raw = cnt[2];
-    if (nb == 0 || nb > n || raw_total + 16 > raw_bound || cnt[3] > E.kb)
-      return fail(LGS_EINTERNAL, "cut of %u entries: %llu blocks, %llu bytes", n,
-                  (unsigned long long)nb, (unsigned long long)raw_total);
-    if (max_raw > 0x7fffffffull)
-      return fail(LGS_EINVAL, "a block of %llu bytes: under 2^31 supported",
-                  (unsigned long long)max_raw);
+    LGS_TRY(build_data(A, h, d, s, in, E.kb, block_size, restart_interval, internal_keys ? 8u : 0u,
+                       compression, true, &D));
+    LGS_HIP(launch_handle_values((const uint64_t*)(d + A.o_hoff), (const uint64_t*)(d + A.o_hsize),
+                                 nullptr, (const uint64_t*)(d + A.K.ioff), (uint32_t)D.nb,
+                                 d + A.o_hval, (uint64_t*)(d + A.o_ivoff),
+                                 (uint32_t*)(d + A.o_ivlen), (uint32_t*)(d + A.o_iklen), s));
   } else {
-    LGS_HIP(hipMemsetAsync(d + K.bf, 0, 4, s));
+    LGS_HIP(hipMemsetAsync(d + A.K.bf, 0, 4, s));
   }
-  // Data blocks (table_builder.c:215-278), framed from file offset 0.
-  uint64_t* d_hoff = (uint64_t*)(d + o_hoff);
-  uint64_t* d_hsize = (uint64_t*)(d + o_hsize);
-  uint64_t data_end = 0;
-  const BlockCut cut2 = K2.at(d, (uint64_t*)(d + o_cnt2));
-  const BlockIn iin{d + o_ikey, cut.ikey_off, (const uint32_t*)(d + o_iklen), d + o_hval,
-                    (const uint64_t*)(d + o_ivoff), (const uint32_t*)(d + o_ivlen), (uint32_t)nb};
-  uint64_t index_len = 0;
-  if (nb) {
-    LGS_HIP(launch_block_emit(in, restart_interval, trim, (uint32_t)nb, B.at(d + o_scr),
-                              cut.block_first, cut.raw_off, cut.raw_len, d + o_raw, cut.ikey_off,
-                              d + o_ikey, s));
-    LGS_TRY(table_write(d + o_raw, cut.raw_off, cut.raw_len, (uint32_t)nb, (uint32_t)max_raw,
-                        compression, 0, d + o_file, d_hoff, d_hsize, (uint64_t*)(d + o_end),
-                        d + o_wscr, WriteScratch((uint32_t)nb, raw_total), s));
-    // The index block's entries (:229-239, :332-341): index key -> handle, one
-    // block whatever its size, restart interval 1 (:87).
-    LGS_HIP(launch_handle_values(d_hoff, d_hsize, cut.ikey_off, (uint32_t)nb, d + o_hval,
-                                 (uint64_t*)(d + o_ivoff), (uint32_t*)(d + o_ivlen),
-                                 (uint32_t*)(d + o_iklen), s));
-    LGS_HIP(launch_block_cut(iin, ~0ull, 1, 0, B.at(d + o_scr), cut2, s));
-    LGS_HIP(hipMemcpyAsync(h + o_cnt2, d + o_cnt2, 8 * kBlockCounts, hipMemcpyDeviceToHost, s));
-    LGS_HIP(hipMemcpyAsync(h + o_end, d + o_end, 8, hipMemcpyDeviceToHost, s));
-    LGS_HIP(hipStreamSynchronize(s));
-    data_end = *(const uint64_t*)(h + o_end);
-    const uint64_t* cnt2 = (const uint64_t*)(h + o_cnt2);
-    index_len = cnt2[1];
-    if (data_end > data_bound || cnt2[0] != 1 || index_len > ibound)
-      return fail(LGS_EINTERNAL, "data blocks end at %llu, index block of %llu bytes",
-                  (unsigned long long)data_end, (unsigned long long)index_len);
-    LGS_HIP(launch_block_emit(iin, 1, 0, 1, B.at(d + o_scr), cut2.block_first, cut2.raw_off,
-                              cut2.raw_len, d + o_iraw, nullptr, nullptr, s));
-  } else {
-    // An index block with no entries (block_builder.c:68, :143-146).
-    index_len = tail_metaindex(h + o_meta, kMetaindexMax, nullptr, 0, 0);
-    LGS_HIP(hipMemcpyAsync(d + o_iraw, h + o_meta, (size_t)index_len, hipMemcpyHostToDevice, s));
-    LGS_HIP(hipStreamSynchronize(s));
-  }
-  // The filter block (:292-299), stored raw after the data blocks.
-  uint64_t at = data_end, filter_size = 0;
-  if (filter) {
-    LGS_TRY(lgs_filter_block_build_dev(in.keys, in.key_off, in.key_len, n, cut.block_first, d_hoff,
-                                       (uint32_t)nb, data_end, bits_per_key, internal_keys,
-                                       d + o_fout, fbound, (uint64_t*)(d + o_fsize), d + o_fscr,
-                                       F.total, s));
-    LGS_HIP(hipMemcpyAsync(h + o_fsize, d + o_fsize, 8, hipMemcpyDeviceToHost, s));
-    LGS_HIP(hipStreamSynchronize(s));
-    filter_size = *(const uint64_t*)(h + o_fsize);
-    if (filter_size > fbound)
-      return fail(LGS_EINTERNAL, "filter block %llu > bound %zu", (unsigned long long)filter_size,
-                  fbound);
-    *(uint64_t*)(h + o_toff) = 0;
-    *(uint32_t*)(h + o_tlen) = (uint32_t)filter_size;
-    LGS_HIP(hipMemcpyAsync(d + o_toff, h + o_toff, 8, hipMemcpyHostToDevice, s));
-    LGS_HIP(hipMemcpyAsync(d + o_tlen, h + o_tlen, 4, hipMemcpyHostToDevice, s));
-    LGS_TRY(table_write(d + o_fout, (const uint64_t*)(d + o_toff), (const uint32_t*)(d + o_tlen), 1,
-                        (uint32_t)filter_size, LGS_NO_COMPRESSION, at, d + o_file + at,
-                        (uint64_t*)(d + o_thoff), (uint64_t*)(d + o_thsize), nullptr, d + o_wscr,
-                        WriteScratch(1, filter_size), s));
-    // The pinned words are reused below: the uploads must have left them.
-    LGS_HIP(hipStreamSynchronize(s));
-    at += filter_size + LGS_TRAILER_SIZE;
-  }
-  // Metaindex (:301-328) and index (:330-344) blocks, both through the
-  // table's compression like every block ldb_tablegen_write_block writes.
-  // The index block grows with the table (C5: 36 MB), and one block is one
-  // wave's work in the encoder, 64 KiB chunk after chunk; the chunks are
-  // independent (snappy.c:370-381), so they are encoded here as items of
-  // their own, as ldb_snappy_encode does, and packed into the block's stream.
-  const size_t meta_len = tail_metaindex(h + o_meta, kMetaindexMax, filter ? kFilterName : nullptr,
-                                         data_end, filter_size);
-  if (meta_len == 0) return fail(LGS_EINTERNAL, "metaindex block does not fit");
-  const bool snappy = compression == LGS_SNAPPY_COMPRESSION;
-  uint64_t* toff = (uint64_t*)(h + o_toff);
-  uint32_t* tlen = (uint32_t*)(h + o_tlen);
-  uint64_t* tenc_off = (uint64_t*)(h + o_tencoff);
-  toff[0] = o_meta;          // offsets from the arena's start
-  toff[1] = o_iraw;
-  tlen[0] = (uint32_t)meta_len;
-  tlen[1] = (uint32_t)index_len;
-  tenc_off[0] = o_tslots;
-  tenc_off[1] = o_tpacked;
-  const uint32_t items = 1 + (uint32_t)((index_len + kChunk - 1) / kChunk);
-  if (items > icap) return fail(LGS_EINTERNAL, "index block of %llu bytes",
-                                (unsigned long long)index_len);
-  uint64_t* it_in = (uint64_t*)(h + o_titems);
-  uint64_t* it_out = it_in + icap;
-  uint32_t* it_len = (uint32_t*)(it_out + icap);
-  uint32_t* it_hdr = it_len + icap;
-  it_in[0] = o_meta;
-  it_len[0] = it_hdr[0] = (uint32_t)meta_len;
-  it_out[0] = o_tslots;
-  size_t slot = o_tslots + chunk_out((uint32_t)meta_len);
-  for (uint32_t j = 1; j < items; ++j) {
-    const uint64_t off = (uint64_t)(j - 1) * kChunk;
-    it_in[j] = o_iraw + off;
-    it_len[j] = (uint32_t)(index_len - off < kChunk ? index_len - off : kChunk);
-    it_hdr[j] = j == 1 ? (uint32_t)index_len : 0xffffffffu;      // snappy.c:368
-    it_out[j] = slot;
-    slot += chunk_out(it_len[j]);
-  }
-  LGS_HIP(hipMemcpyAsync(d + o_meta, h + o_meta, o_cnt - o_meta, hipMemcpyHostToDevice, s));
-  uint64_t* part = (uint64_t*)(d + o_tpart);
-  uint32_t* enc_len = (uint32_t*)(d + o_tenclen);
-  uint32_t* enc_len2 = (uint32_t*)(d + o_tenclen2);
-  if (snappy) {
-    const uint64_t* d_out = (const uint64_t*)(d + o_titems) + icap;
-    const uint32_t* d_len = (const uint32_t*)(d_out + icap);
-    EncodeArgs ea{d, (const uint64_t*)(d + o_titems), d_len, d, d_out, enc_len, d_len + icap,
-                  nullptr, items, nullptr};
-    const uint32_t ichunk = (uint32_t)(index_len < kChunk ? index_len : kChunk);
-    LGS_HIP(launch_encode(ea, meta_len > ichunk ? (uint32_t)meta_len : ichunk, s));
-    LGS_HIP(launch_scan(2, nullptr, enc_len + 1, part, 0, (uint64_t*)(d + o_tpoff),
-                        (uint64_t*)(d + o_tptotal), items - 1, s));
-    LGS_HIP(launch_pack(d, d_out + 1, enc_len + 1, d + o_tpacked, (const uint64_t*)(d + o_tpoff),
-                        items - 1, s));
-    LGS_HIP(launch_pair_lens(enc_len, (const uint64_t*)(d + o_tptotal), enc_len2, s));
-  }
-  LGS_HIP(launch_scan(1, (const uint32_t*)(d + o_tlen), snappy ? enc_len2 : nullptr, part, at,
-                      (uint64_t*)(d + o_tfoff), (uint64_t*)(d + o_end), 2, s));
-  const FrameArgs fa{d, (const uint64_t*)(d + o_toff), (const uint32_t*)(d + o_tlen), d,
-                     (const uint64_t*)(d + o_tencoff), snappy ? enc_len2 : nullptr,
-                     d + o_file + at, at, (const uint64_t*)(d + o_tfoff),
-                     (uint64_t*)(d + o_thoff), (uint64_t*)(d + o_thsize), 2};
-  LGS_HIP(launch_frame(fa, s));
-  LGS_HIP(hipMemcpyAsync(h + o_end, d + o_end, pin_end - o_end, hipMemcpyDeviceToHost, s));
+  TailFile f;
+  f.nb = (uint32_t)D.nb;
+  f.ne = n;
+  f.len_known = n == 0;
+  f.block_off = (const uint64_t*)(d + A.o_hoff);
+  f.image = d + A.o_stream;
+  f.d_size = (uint64_t*)(d + A.o_size);
+  LGS_TRY(build_tail(A, h, d, s, in, compression, bits_per_key, internal_keys, f));
+  LGS_HIP(hipMemcpyAsync(h + A.o_size, d + A.o_size, 8, hipMemcpyDeviceToHost, s));
   LGS_HIP(hipStreamSynchronize(s));
-  const uint64_t end = *(const uint64_t*)(h + o_end);
-  const uint64_t* thoff = (const uint64_t*)(h + o_thoff);
-  const uint64_t* thsize = (const uint64_t*)(h + o_thsize);
-  if (end > img_bound)
-    return fail(LGS_EINTERNAL, "table of %llu bytes > bound %zu", (unsigned long long)end, img_bound);
-  *file_size = (size_t)(end + kFooterSize);
-  if (end + kFooterSize > file_cap)
-    return fail(LGS_ENOSPC, "table needs %llu bytes, file_cap %zu",
-                (unsigned long long)(end + kFooterSize), file_cap);
-  LGS_HIP(hipMemcpyAsync(file, d + o_file, (size_t)end, hipMemcpyDeviceToHost, s));
+  const uint64_t size = *(const uint64_t*)(h + A.o_size);
+  if (size > img_bound)
+    return fail(LGS_EINTERNAL, "table of %llu bytes > bound %zu", (unsigned long long)size, img_bound);
+  *file_size = (size_t)size;
+  if (size > file_cap)
+    return fail(LGS_ENOSPC, "table needs %llu bytes, file_cap %zu", (unsigned long long)size,
+                file_cap);
+  LGS_HIP(hipMemcpyAsync(file, d + A.o_stream, (size_t)size, hipMemcpyDeviceToHost, s));
   LGS_HIP(hipStreamSynchronize(s));
-  tail_footer(file + end, thoff[0], thsize[0], thoff[1], thsize[1]);   // :346-362
+  return LGS_OK;
+}
+
+size_t lgs_tables_build_bound(uint32_t n, uint64_t key_bytes, uint64_t value_bytes,
+                              int bits_per_key, uint64_t max_file_size, uint32_t* max_files) {
+  // Every file but the last holds at least max_file_size bytes of data blocks,
+  // and every file at least one entry; per file the tail's constant parts, the
+  // spare bytes and the alignment of file_slot (under 320 bytes).
+  const uint64_t data = key_bytes + value_bytes + 19ull * n + (uint64_t)LGS_TRAILER_SIZE * n;
+  uint64_t files = max_file_size ? data / max_file_size + 1 : n;
+  if (files > n) files = n;
+  if (max_files) *max_files = (uint32_t)files;
+  return (size_t)(lgs_table_build_bound(n, key_bytes, value_bytes, bits_per_key) + 320 * files);
+}
+
+int lgs_tables_build_dev(const uint8_t* d_keys, const uint64_t* d_key_off, const uint32_t* d_key_len,
+                         const uint8_t* d_vals, const uint64_t* d_val_off, const uint32_t* d_val_len,
+                         uint32_t n, uint64_t key_bytes, uint64_t value_bytes, uint64_t block_size,
+                         uint32_t restart_interval, int compression, int bits_per_key,
+                         int internal_keys, uint64_t max_file_size, uint8_t* d_files,
+                         size_t files_cap, uint64_t* d_file_off, uint64_t* d_file_size,
+                         uint32_t* d_file_first, uint32_t files_cap_count, uint32_t* n_files,
+                         uint64_t* files_bytes, void* stream) {
+  LGS_TRY(build_args(n, restart_interval, compression, bits_per_key, internal_keys));
+  if (!n_files || !files_bytes) return fail(LGS_EINVAL, "NULL argument");
+  *n_files = 0;
+  *files_bytes = 0;
+  // A file closed after every entry ends with a pending block, not after a
+  // flush (db_impl.c:1417-1425 with table_builder.c:251-254).
+  if (max_file_size == 0) return fail(LGS_EINVAL, "max_file_size must be at least 1");
+  if (n == 0) return LGS_OK;
+  if (!d_keys || !d_key_off || !d_key_len || !d_vals || !d_val_off || !d_val_len)
+    return fail(LGS_EINVAL, "NULL argument");
+  if (key_bytes > (1ull << 62) || value_bytes > (1ull << 62))
+    return fail(LGS_EINVAL, "key_bytes or value_bytes out of range");
+  Lease lease(batch_pool());
+  LGS_TRY(lease.acquire());
+  Ctx& c = lease.ctx();
+  Layout L;
+  BuildLayout A;
+  LGS_TRY(A.take(L, n, key_bytes, value_bytes, bits_per_key, false, true));
+  LGS_TRY(ctx_reserve(c, L.at, A.pin_end));
+  uint8_t* h = c.h_buf;
+  uint8_t* d = c.d_buf;
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t trim = internal_keys ? 8u : 0u;
+  const BlockIn in{d_keys, d_key_off, d_key_len, d_vals, d_val_off, d_val_len, n};
+  DataBlocks D;
+  LGS_TRY(build_data(A, h, d, s, in, key_bytes, block_size, restart_interval, trim, compression,
+                     false, &D));
+  const uint32_t nb = (uint32_t)D.nb;
+  // The files (second synchronisation: their number; third: one row each).
+  const BlockBuildScratch B(n);
+  const BlockCut cut = A.K.at(d, (uint64_t*)(d + A.o_cnt));
+  const FilePlan P = A.plan_at(d);
+  const uint64_t* d_hoff = (const uint64_t*)(d + A.o_hoff);
+  const uint64_t* d_hsize = (const uint64_t*)(d + A.o_hsize);
+  LGS_HIP(launch_file_plan(in, trim, nb, d_hoff, d_hsize, max_file_size, B.at(d + A.o_scr), cut,
+                           P, s));
+  LGS_HIP(hipMemcpyAsync(h + A.o_nfiles, d + A.o_nfiles, 8, hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipStreamSynchronize(s));
+  const uint64_t nf = *(const uint64_t*)(h + A.o_nfiles);
+  if (nf == 0 || nf > nb) return fail(LGS_EINTERNAL, "%llu files of %u blocks",
+                                      (unsigned long long)nf, nb);
+  std::vector<uint32_t> fblock(nf + 1), fentry(nf + 1);
+  std::vector<uint64_t> fbegin(nf + 1), fikey(nf + 1), foff(nf);
+  LGS_HIP(hipMemcpyAsync(fblock.data(), P.file_block, 4 * (nf + 1), hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipMemcpyAsync(fentry.data(), P.file_entry, 4 * (nf + 1), hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipMemcpyAsync(fbegin.data(), P.file_start, 8 * (nf + 1), hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipMemcpyAsync(fikey.data(), P.file_ikey, 8 * (nf + 1), hipMemcpyDeviceToHost, s));
+  LGS_HIP(hipStreamSynchronize(s));
+  uint64_t total = 0;
+  for (uint64_t f = 0; f < nf; ++f) {
+    if (fblock[f + 1] <= fblock[f] || fentry[f + 1] <= fentry[f] || fbegin[f + 1] <= fbegin[f] ||
+        fikey[f + 1] < fikey[f] || fblock[f + 1] > nb || fentry[f + 1] > n ||
+        fbegin[f + 1] > A.data_bound || fikey[f + 1] > key_bytes)
+      return fail(LGS_EINTERNAL, "file %llu of the plan is out of order", (unsigned long long)f);
+    foff[f] = total;
+    total = align_up((size_t)(total + file_slot(fbegin[f + 1] - fbegin[f], fentry[f + 1] - fentry[f],
+                                                fblock[f + 1] - fblock[f],
+                                                fikey[f + 1] - fikey[f], bits_per_key)), 16);
+  }
+  if (fblock[0] != 0 || fblock[nf] != nb || fentry[nf] != n)
+    return fail(LGS_EINTERNAL, "the file plan does not cover the blocks");
+  *n_files = (uint32_t)nf;
+  *files_bytes = total;
+  if (nf > files_cap_count || total > files_cap)
+    return fail(LGS_ENOSPC, "%llu files of %llu bytes (files_cap_count %u, files_cap %zu)",
+                (unsigned long long)nf, (unsigned long long)total, files_cap_count, files_cap);
+  if (!d_files || !d_file_off || !d_file_size || !d_file_first)
+    return fail(LGS_EINVAL, "NULL argument");
+  // Everything from here is queued behind the uploads of this function's own
+  // arrays and works in the pooled arena, so the stream is drained on every
+  // way out.
+  const int rc = [&]() -> int {
+    LGS_HIP(hipMemcpyAsync(d_file_off, foff.data(), 8 * nf, hipMemcpyHostToDevice, s));
+    LGS_HIP(hipMemcpyAsync(d_file_first, P.file_entry, 4 * (nf + 1), hipMemcpyDeviceToDevice, s));
+    // Index keys (the files' last blocks now end in short successors), handle
+    // values from each file's start, and the data regions to their images.
+    LGS_HIP(launch_block_ikeys(in, trim, nb, B.at(d + A.o_scr), cut.block_first, cut.ikey_off,
+                               d + A.o_ikey, s));
+    LGS_HIP(launch_handle_values(d_hoff, d_hsize, P.fstart, cut.ikey_off, nb, d + A.o_hval,
+                                 (uint64_t*)(d + A.o_ivoff), (uint32_t*)(d + A.o_ivlen),
+                                 (uint32_t*)(d + A.o_iklen), s));
+    LGS_HIP(launch_file_place(P, d_file_off, (uint64_t*)(d + A.p_dst), nb, s));
+    LGS_HIP(launch_pack(d + A.o_stream, d_hoff, P.flen, d_files, (const uint64_t*)(d + A.p_dst), nb,
+                        s));
+    for (uint64_t f = 0; f < nf; ++f) {
+      TailFile t;
+      t.b0 = fblock[f];
+      t.nb = fblock[f + 1] - fblock[f];
+      t.ne = fentry[f + 1] - fentry[f];
+      t.len_known = true;
+      t.data_len = fbegin[f + 1] - fbegin[f];
+      t.block_off = P.rel + t.b0;
+      t.image = d_files + foff[f];
+      t.d_size = d_file_size + f;
+      LGS_TRY(build_tail(A, h, d, s, in, compression, bits_per_key, internal_keys, t));
+    }
+    return LGS_OK;
+  }();
+  const hipError_t drained = hipStreamSynchronize(s);
+  LGS_TRY(rc);
+  LGS_HIP(drained);
   return LGS_OK;
 }
 

@@ -30,8 +30,10 @@ the batched C ABI that does both for many blocks per launch
 * ``merge_runs`` / ``merge_runs_host`` -- ``ldb_mergeiter_first`` + ``_next``
   until invalid over sorted runs (src/table/merger.c) and the drop loop of
   ``ldb_do_compaction_work`` (src/db_impl.c:1369-1396);
-* ``compact_tables``  -- scan, merge and drop, build: one compaction's output
-  table from its input tables;
+* ``build_tables_dev`` -- ``ldb_tablegen_*`` over entries in device memory, cut
+  into the files of db_impl.c:1399-1425 by ``max_output_file_size``;
+* ``compact_to_files`` / ``compact_tables`` -- scan, merge and drop, build:
+  one compaction's output files (or one table) from its input tables;
 * ``index_host``      -- ``ldb_table_open``'s footer, index-block handles and
   metaindex filter handle (src/table/table.c:78-180), the handles the batched
   read takes.
@@ -55,7 +57,7 @@ _L = _native.lib()
 
 __all__ = [
     "crc32c_batch", "write_blocks", "read_blocks", "write_blocks_host", "read_blocks_host",
-    "index_host", "FILTER_NAME", "seek_blocks_host", "block_entries", "block_entries_host", "ScanError", "merge_runs", "merge_runs_host", "compact_tables", "MergeError", "get_host", "open_table", "OpenTable", "build_blocks", "build_blocks_host", "build_table_host",
+    "index_host", "FILTER_NAME", "seek_blocks_host", "block_entries", "block_entries_host", "ScanError", "merge_runs", "merge_runs_host", "compact_tables", "compact_to_files", "build_tables_dev", "MergeError", "get_host", "open_table", "OpenTable", "build_blocks", "build_blocks_host", "build_table_host",
     "LGS_NO_COMPRESSION", "LGS_SNAPPY_COMPRESSION", "LGS_TRAILER_SIZE", "LGS_ST_OK",
     "LGS_ST_CORRUPT", "LGS_ST_NOSPACE", "LGS_ST_IOERR", "LGS_ST_BADCRC", "LGS_ST_BADTYPE",
     "LGS_GET_NOTFOUND", "LGS_GET_FOUND", "LGS_GET_DELETED", "LGS_GET_CORRUPT",
@@ -942,51 +944,140 @@ def merge_runs_host(runs, internal_keys: bool = False, drop: bool = False,
     return entries, [(int(out[6][i]), int(out[7][i])) for i in range(n)], int(needed[4])
 
 
-def compact_tables(tables, smallest_snapshot: int, drop_deletions: bool, block_size: int = 4096,
-                   restart_interval: int = 16, compression: int = LGS_SNAPPY_COMPRESSION,
-                   bits_per_key: int = 0, verify: bool = True) -> bytes:
-    """One compaction's output table from its input table images, in the
+_NO_SPLIT = (1 << 64) - 1
+
+
+def build_tables_dev(run, block_size: int = 4096, restart_interval: int = 16,
+                     compression: int = LGS_SNAPPY_COMPRESSION, bits_per_key: int = 0,
+                     internal_keys: bool = False, max_file_size: int = _NO_SPLIT, stream=None):
+    """The .ldb files a compaction writes for sorted entries in device memory,
+    left in device memory (lgs_tables_build_dev): lcdb closes an output file
+    once ldb_tablegen_size reaches ``max_file_size`` (db_impl.c:1417-1425);
+    the default gives one file, ``build_table_host``'s image.
+
+    ``run`` is a dict as ``merge_runs`` / ``block_entries`` return it (``keys``,
+    ``key_off``, ``key_len``, ``vals``, ``val_off``, ``val_len`` and the ints
+    ``n``, ``key_bytes``, ``val_bytes``).  Returns a dict: ``files`` (uint8,
+    the images), ``file_off`` / ``file_size`` (int64, n_files), ``file_first``
+    (int32, n_files + 1: file f holds entries file_first[f]:file_first[f+1])
+    and the int ``n_files``.  No entries give no file.  The stream is drained
+    when it returns."""
+    import ctypes as C
+    torch = _torch()
+    n = int(run["n"]) if "n" in run else int(run["key_len"].numel())
+    dev = run["keys"].device
+    kb = int(run["key_bytes"]) if "key_bytes" in run else int(run["key_len"].sum())
+    vb = int(run["val_bytes"]) if "val_bytes" in run else int(run["val_len"].sum())
+    max_files = C.c_uint32(0)
+    cap = int(_L.lgs_tables_build_bound(n, kb, vb, int(bits_per_key), int(max_file_size),
+                                        C.byref(max_files)))
+    files = torch.empty(cap + 16, dtype=torch.uint8, device=dev)
+    nf_cap = max(int(max_files.value), 1)
+    file_off = torch.zeros(nf_cap, dtype=torch.int64, device=dev)
+    file_size = torch.zeros(nf_cap, dtype=torch.int64, device=dev)
+    file_first = torch.zeros(nf_cap + 1, dtype=torch.int32, device=dev)
+    nf, used = C.c_uint32(0), C.c_uint64(0)
+    check(_L.lgs_tables_build_dev(*(run[f].data_ptr() for f in
+                                    ("keys", "key_off", "key_len", "vals", "val_off", "val_len")),
+                                  n, kb, vb, int(block_size), int(restart_interval),
+                                  int(compression), int(bits_per_key), 1 if internal_keys else 0,
+                                  int(max_file_size), files.data_ptr(), cap, file_off.data_ptr(),
+                                  file_size.data_ptr(), file_first.data_ptr(), nf_cap,
+                                  C.byref(nf), C.byref(used), _stream_ptr(stream)),
+          "lgs_tables_build_dev")
+    if stream is not None:
+        for t in (files, file_off, file_size, file_first):
+            t.record_stream(stream)
+    f = int(nf.value)
+    return {"files": files, "file_off": file_off[:f], "file_size": file_size[:f],
+            "file_first": file_first[:f + 1], "n_files": f, "files_bytes": int(used.value)}
+
+
+def _scan_runs(tables, bits_per_key, verify, opened):
+    runs = []
+    for img in tables:
+        t = open_table(img, internal_keys=True, resident=True,
+                       filter_name=FILTER_NAME if bits_per_key else None)
+        opened.append(t)
+        nxt = 0
+        while True:
+            r = t.scan_dev(first_block=nxt, max_blocks=65536, verify=verify)
+            bad = r["index_status"] if r["at_end"] else LGS_ST_OK
+            if bad == LGS_ST_OK and r["blocks_done"]:
+                st = r["block_status"].cpu().numpy()
+                bad = LGS_ST_OK if (st == LGS_ST_OK).all() else int(st[st != LGS_ST_OK][0])
+            if bad != LGS_ST_OK:
+                e = ScanError(f"compaction input ended with status {bad}")
+                e.status = bad
+                raise e
+            runs.append(r)
+            nxt = r["next_block"]
+            if r["at_end"]:
+                break
+    return runs
+
+
+def compact_to_files(tables, smallest_snapshot: int, drop_deletions: bool, block_size: int = 4096,
+                     restart_interval: int = 16, compression: int = LGS_SNAPPY_COMPRESSION,
+                     bits_per_key: int = 0, verify: bool = True,
+                     max_output_file_size: int = 2 << 20):
+    """One compaction's output files from its input table images, in the
     order ldb_inputiter_create hands them to the merging iterator (newest
     level-0 file first): ``OpenTable.scan_dev`` per table, ``merge_runs``
-    with internal keys and the drop rule, then ``build_table_host``.
+    with internal keys and the drop rule, ``build_tables_dev``; only the
+    finished images and two keys per file come back to the host.
 
     ``drop_deletions`` is ldb_compaction_is_base_level_for_key for every key
-    of the call.  The whole output is one file: should_stop_before and
-    max_output_file_size are not applied.  Between the merge and the build
-    the kept entries make one round trip through host memory; a build entry
-    point that takes entries in device memory is what removes it."""
+    of the call; ``max_output_file_size`` is the compaction's
+    (db_impl.c:1417-1425).  should_stop_before is not applied.
+    Returns one dict per file, in file order: ``image`` (bytes), ``smallest``
+    and ``largest`` (the internal keys of its first and last entry) and
+    ``entries``: what ldb_edit_add_file takes.  No kept entry, no file."""
     torch = _torch()
-    runs, opened = [], []
+    opened = []
     try:
-        for img in tables:
-            t = open_table(img, internal_keys=True, resident=True,
-                           filter_name=FILTER_NAME if bits_per_key else None)
-            opened.append(t)
-            nxt = 0
-            while True:
-                r = t.scan_dev(first_block=nxt, max_blocks=65536, verify=verify)
-                bad = r["index_status"] if r["at_end"] else LGS_ST_OK
-                if bad == LGS_ST_OK and r["blocks_done"]:
-                    st = r["block_status"].cpu().numpy()
-                    bad = LGS_ST_OK if (st == LGS_ST_OK).all() else int(st[st != LGS_ST_OK][0])
-                if bad != LGS_ST_OK:
-                    e = ScanError(f"compaction input ended with status {bad}")
-                    e.status = bad
-                    raise e
-                runs.append(r)
-                nxt = r["next_block"]
-                if r["at_end"]:
-                    break
+        runs = _scan_runs(tables, bits_per_key, verify, opened)
         m = merge_runs(runs, internal_keys=True, drop=True, smallest_snapshot=smallest_snapshot,
                        drop_deletions=drop_deletions)
-        torch.cuda.synchronize()
-        n = m["n"]
-        entries = _unpack_entries(m["keys"].cpu().numpy(), m["key_off"].cpu().numpy(),
-                                  m["key_len"].cpu().numpy().view(np.uint32),
-                                  m["vals"].cpu().numpy(), m["val_off"].cpu().numpy(),
-                                  m["val_len"].cpu().numpy().view(np.uint32), n)
+        b = build_tables_dev(m, block_size, restart_interval, compression, bits_per_key,
+                             internal_keys=True, max_file_size=max_output_file_size)
+        nf = b["n_files"]
+        if nf == 0:
+            return []
+        first = b["file_first"].to(torch.int64)
+        ends = torch.stack((first[:-1], first[1:] - 1), 1).reshape(-1)   # per file: first, last entry
+        koff, klen = m["key_off"][ends], m["key_len"][ends].to(torch.int64)
+        span = torch.arange(int(klen.max()), device=koff.device)
+        at = (koff[:, None] + span[None, :]).clamp_(max=m["keys"].numel() - 1)
+        keys, klen = m["keys"][at].cpu().numpy(), klen.cpu().numpy()
+        off, size, first = (b[k].cpu().numpy() for k in ("file_off", "file_size", "file_first"))
+        lo, hi = int(off[0]), int(off[-1] + size[-1])
+        host = b["files"][lo:hi].cpu().numpy()
     finally:
         for t in opened:
             t.close()
-    return build_table_host(entries, block_size, restart_interval, compression, bits_per_key,
-                            internal_keys=True)
+    out = []
+    for f in range(nf):
+        at = int(off[f]) - lo
+        out.append({"image": host[at:at + int(size[f])].tobytes(),
+                    "smallest": keys[2 * f, :int(klen[2 * f])].tobytes(),
+                    "largest": keys[2 * f + 1, :int(klen[2 * f + 1])].tobytes(),
+                    "entries": int(first[f + 1]) - int(first[f])})
+    return out
+
+
+def compact_tables(tables, smallest_snapshot: int, drop_deletions: bool, block_size: int = 4096,
+                   restart_interval: int = 16, compression: int = LGS_SNAPPY_COMPRESSION,
+                   bits_per_key: int = 0, verify: bool = True) -> bytes:
+    """One compaction's output as one table: ``compact_to_files`` with no
+    limit on the output file's size (should_stop_before and
+    max_output_file_size are not applied), so scan, merge and build all stay
+    in device memory and only the image is downloaded.  A compaction that
+    keeps no entry gives lcdb's empty table, as ``build_table_host`` does."""
+    files = compact_to_files(tables, smallest_snapshot, drop_deletions, block_size,
+                             restart_interval, compression, bits_per_key, verify,
+                             max_output_file_size=_NO_SPLIT)
+    if not files:
+        return build_table_host([], block_size, restart_interval, compression, bits_per_key,
+                                internal_keys=True)
+    return files[0]["image"]
