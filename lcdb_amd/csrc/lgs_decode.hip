@@ -702,6 +702,17 @@ __device__ __forceinline__ void pair_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// A job record (16 bytes, 16-byte aligned in LDS) as one access.
+__device__ __forceinline__ RingJob job_rd(const RingJob* p) {
+  const u32x4 v = *reinterpret_cast<const u32x4*>(p);
+  RingJob jb;
+  jb.off = v.x;
+  jb.cnt = v.y;
+  jb.plo = v.z;
+  jb.phil = v.w;
+  return jb;
+}
+
 // One op (a piece of <= 64 bytes, snappy.c:210-331) of a lane whose bytes are
 // in LDS: a literal from offset lo of the input ring ib, a copy from the
 // output ring.
@@ -745,7 +756,23 @@ __device__ __forceinline__ void pair_piece(uint8_t* ob, const uint8_t* ib, uint3
       const uint32_t o = lo + 16 * k;
       return lit ? ib + (o >= pairq::kIn ? o - pairq::kIn : o) : cp + 16 * k;
     };
+    // Every chunk is read before any is written, so the piece crosses one LDS
+    // round trip and write k goes out when read k lands.  The source lies
+    // wholly below made (dist >= piece; a pattern uses chunk 0 alone) and a
+    // source chunk shares ring slots only with a later destination chunk
+    // (dist <= kNear), so it is intact until the piece's first write.  Only
+    // the lanes that have chunk k read it: an unaligned b128 costs by the
+    // lanes it moves, also those that ride along at an aligned address
+    // (SQ_LDS_UNALIGNED_STALL +30 % that way).
     const u32x4 c0 = lrd16(src(0));
+    u32x4 c1 = {0, 0, 0, 0}, c2 = c1, c3 = c1;
+    if (!pat & (piece > 16)) {
+      c1 = lrd16(src(1));
+      if (piece > 32) {
+        c2 = lrd16(src(2));
+        if (piece > 48) c3 = lrd16(src(3));
+      }
+    }
     // Period 1/2/4/8: the dist bytes before made as a 16-byte pattern.
     const uint32_t w1 = __builtin_amdgcn_perm(c0.x, c0.x, 0x00000000u);
     const uint32_t w2 = __builtin_amdgcn_perm(c0.x, c0.x, 0x01000100u);
@@ -753,11 +780,9 @@ __device__ __forceinline__ void pair_piece(uint8_t* ob, const uint8_t* ib, uint3
     const uint32_t py = dist == 8 ? c0.y : px;
     const u32x4 pv = {px, py, px, py};
     out_put(ob, made, pat ? pv : c0);
-    // Chunk k is read just before chunk k is written: a source chunk can
-    // share ring slots only with a later destination chunk (dist <= kNear).
-    if (piece > 16) out_put(ob, made + 16, pat ? pv : lrd16(src(1)));
-    if (piece > 32) out_put(ob, made + 32, pat ? pv : lrd16(src(2)));
-    if (piece > 48) out_put(ob, made + 48, pat ? pv : lrd16(src(3)));
+    if (piece > 16) out_put(ob, made + 16, pat ? pv : c1);
+    if (piece > 32) out_put(ob, made + 32, pat ? pv : c2);
+    if (piece > 48) out_put(ob, made + 48, pat ? pv : c3);
   }
 }
 
@@ -933,8 +958,12 @@ __global__ __launch_bounds__(128) void decode_pair_kernel(
         order();
         ra0 = rm0 = ra1 = rm1 = kNone;
         const uint32_t w = lane & 3u;
+        // Both records are read before either is used (one round trip; one
+        // past `total` is stale and not used), then both loads are issued.
+        const RingJob jb0 = job_rd(&s_rjob[lane >> 2]);
+        const RingJob jb1 = job_rd(&s_rjob[16 + (lane >> 2)]);
         if ((lane >> 2) < total) {
-          const RingJob jb = s_rjob[lane >> 2];
+          const RingJob jb = jb0;
           const gptr<const uint8_t> g = (gptr<const uint8_t>)jb.ptr();
           // (A granule past the stream reloads the chunk's first: never consumed.)
           rv0 = ld16(g + (16 * w < jb.cnt ? 16 * w : 0u));
@@ -943,7 +972,7 @@ __global__ __launch_bounds__(128) void decode_pair_kernel(
           rm0 = r == 0 ? ra0 + kIn : kNone;
         }
         if (16 + (lane >> 2) < total) {
-          const RingJob jb = s_rjob[16 + (lane >> 2)];
+          const RingJob jb = jb1;
           const gptr<const uint8_t> g = (gptr<const uint8_t>)jb.ptr();
           rv1 = ld16(g + (16 * w < jb.cnt ? 16 * w : 0u));
           const uint32_t r = jb.off + 16 * w;
@@ -1080,17 +1109,20 @@ __global__ __launch_bounds__(128) void decode_pair_kernel(
       for (uint32_t base = 0; base < total; base += 64 / kFL) {
         const uint32_t jj = base + lane / kFL, w = lane % kFL;
         // jj < base + 64 / kFL <= kBlocks: the record is in range (stale past total).
-        const RingJob jb = s_fjob[jj];
+        const RingJob jb = job_rd(&s_fjob[jj]);
         if ((jj < total) & (16 * w < jb.cnt)) {
-          const uint8_t* rb = s_out + (jb.lane() & (kBlocks - 1)) * kOutStride + 16 +
-                              ((uint32_t)jb.ptr() & 15u);
+          const uint8_t* jpark = s_out + (jb.lane() & (kBlocks - 1)) * kOutStride;
+          const uint8_t* rb = jpark + 16 + ((uint32_t)jb.ptr() & 15u);
           const gptr<uint8_t> g = (gptr<uint8_t>)jb.ptr() + jb.off;
+          // The job's granules are read together (one round trip); one past
+          // the job reads the block's pad, aligned, and is never stored.  (A
+          // job's reads end on the destination's 16-byte boundaries, so all
+          // but a block's first are aligned, and most jobs are whole lines.)
           u32x4 v[kFG];
 #pragma unroll
           for (uint32_t k = 0; k < kFG; ++k) {
             const uint32_t o = 16 * (w + kFL * k);
-            if (k > 0) v[k] = v[0];               // (granule 0 is inside the job)
-            if (k == 0 || o < jb.cnt) v[k] = lrd16(rb + ((jb.off + o) & (kOutRing - 1)));
+            v[k] = lrd16(o < jb.cnt ? rb + ((jb.off + o) & (kOutRing - 1)) : jpark);
           }
 #pragma unroll
           for (uint32_t k = 0; k < kFG; ++k) {
