@@ -27,6 +27,7 @@ import random
 import struct
 import sys
 
+RESTARTS = [1, 2, 3, 5, 7, 16, 17, 64]            # the self-checks' restart intervals (tests/build_sweep.py)
 MAX_SEQ_SEEK = ((((1 << 56) - 1) << 8) | 1).to_bytes(8, "little")   # dbformat.h: pack_seqtype
 
 
@@ -162,24 +163,23 @@ def parallel_first(entries, block_size: int, restart_interval: int = 16):
         C[step:] = C[step:] + C[:-step].copy()
         step *= 2
 
-    def c_at(i):
-        return int(C[i]) if i >= 0 else 0
+    s = np.arange(n, dtype=np.int64)
+    c_before = np.where(s >= R, C[np.maximum(s - R, 0)], 0)
 
-    def est(s, j):
+    def est(j):                                    # of the block s..j, for every s at once
         m = j - s + 1
-        return int(S[j + 1] - S[s]) + c_at(s + (j - s) // R * R) - c_at(s - R) + 4 * -(-m // R) + 4
+        return S[j + 1] - S[s] + C[s + (j - s) // R * R] - c_before + 4 * -(-m // R) + 4
 
+    lo, hi = s.copy(), np.full(n, n, dtype=np.int64)
+    while (lo < hi).any():                         # first j with est >= block_size, else n
+        mid = np.minimum((lo + hi) // 2, n - 1)
+        open_ = lo < hi
+        reached = est(mid) >= block_size
+        hi = np.where(open_ & reached, mid, hi)
+        lo = np.where(open_ & ~reached, mid + 1, lo)
     nxt = np.zeros(n + 1, dtype=np.int64)
     nxt[n] = n
-    for s in range(n):
-        lo, hi = s, n                              # first j with est >= block_size, else n
-        while lo < hi:
-            mid = (lo + hi) // 2
-            if est(s, mid) >= block_size:
-                hi = mid
-            else:
-                lo = mid + 1
-        nxt[s] = min(lo + 1, n)
+    nxt[:n] = np.minimum(lo + 1, n)
     mark = np.zeros(n + 1, dtype=bool)
     mark[0] = True
     J = nxt
@@ -210,7 +210,7 @@ def main() -> None:
         n = rng.choice([0, 1, 2, 15, 16, 17, 33, 100, 700]) if t % 3 else rng.randrange(0, 700)
         e = random_entries(rng, n)
         bs = rng.choice([1, 20, 64, 256, 1024, 4096, 65536])
-        R = rng.choice([1, 2, 16])
+        R = rng.choice(RESTARTS)
         want, _ = serial_blocks(e, bs, R)
         got = parallel_first(e, bs, R)
         assert got == want, (t, n, bs, R)

@@ -35,7 +35,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from sim_block_cut import BlockGen, random_entries, separator, serial_blocks, successor, varint  # noqa: E402
+from sim_block_cut import RESTARTS, BlockGen, random_entries, separator, serial_blocks, successor, varint  # noqa: E402
 
 FILTER_KEY = b"filter.leveldb.BuiltinBloomFilter2"
 MAGIC = 0xdb4775248b80fb57                                       # format.h:26
@@ -169,7 +169,7 @@ def main() -> None:
         n = rng.choice([1, 2, 17, 100, 400])
         e = random_entries(rng, n)
         bs = rng.choice([1, 64, 256, 1024])
-        R = rng.choice([1, 2, 16])
+        R = rng.choice(RESTARTS)
         comp = rng.choice([0, 1])
         mx = rng.choice([1, 100, 300, 1024, 5000, NO_SPLIT])
         want, images = split_serial(e, bs, R, comp, rng.choice([0, 10]), False, mx)
