@@ -722,20 +722,26 @@ int lgs_table_scan_dev(lgs_table *table, int verify_checksums, const uint8_t *st
  *
  * Preconditions: every run is non-decreasing under the comparator, and with
  * internal_keys every key has at least 8 bytes (the builder's contract; the
- * reference asserts it, so db_impl.c:1363-1367's "do not hide error keys"
- * branch cannot be reached from here).  The plan checks both with a compare
- * of each entry and its predecessor: d_counts[5] is the lowest-numbered
- * offending run, or ~0 when there is none.  When it is set the other counts
- * and everything lgs_merge_emit_dev writes are undefined (but inside the
- * buffers the counts size); lgs_merge_host returns LGS_EINVAL and writes
- * nothing.
+ * reference asserts it).  The plan checks both with a compare of each entry
+ * and its predecessor: d_counts[5] is the lowest-numbered offending run, or
+ * ~0 when there is none.  When it is set the other counts and everything
+ * lgs_merge_emit_dev writes are undefined (but inside the buffers the counts
+ * size); lgs_merge_host returns LGS_EINVAL and writes nothing.  A tag whose
+ * type byte is above 1 is not an error of the call: ldb_put cannot write one,
+ * but table files can hold them and lcdb's repairer keeps such tables.
  *
- * Drop rule (drop = 1, internal_keys = 1 only; db_impl.c:1369-1396), walking
- * the merged order: last_seq is LDB_MAX_SEQUENCE (2^56 - 1) at the first entry
- * of a user key, otherwise the sequence of the entry just before, dropped or
- * not.  An entry is dropped when last_seq <= smallest_snapshot (A), or else
- * when it is a deletion (type 0) with sequence <= smallest_snapshot and
- * drop_deletions is set.  drop_deletions stands for
+ * Drop rule (drop = 1, internal_keys = 1 only; db_impl.c:1363-1397), walking
+ * the merged order.  An entry whose type byte is above 1 fails
+ * ldb_pkey_import (dbformat.c:86-107), the other way into "do not hide error
+ * keys" (:1363-1367): it is never dropped, and lcdb forgets the current user
+ * key, so the entry behind it counts as a first occurrence.  For the others
+ * last_seq is LDB_MAX_SEQUENCE (2^56 - 1) at the first entry of a user key
+ * and behind an unparsable entry, otherwise the sequence of the entry just
+ * before, dropped or not.  An entry is dropped when last_seq <=
+ * smallest_snapshot (A), or else when it is a deletion (type 0) with
+ * sequence <= smallest_snapshot and drop_deletions is set.  The merge order
+ * is the comparator's, by the raw tag, whatever the type byte.
+ * drop_deletions stands for
  * ldb_compaction_is_base_level_for_key, which the caller asserts for the
  * whole call: a caller whose answer differs by key range splits the merge by
  * range.  With drop = 0 nothing is dropped, and smallest_snapshot and

@@ -1,7 +1,7 @@
 // lgs_merge.hip -- gfx950 kernels of the merge of sorted runs:
 // ldb_mergeiter_first + _next until invalid (merger.c:107-128, 155-194) over
 // up to 64 runs in the block builder's input layout, and the drop loop of
-// ldb_do_compaction_work (db_impl.c:1369-1396) over the merged order.
+// ldb_do_compaction_work (db_impl.c:1363-1397) over the merged order.
 //
 // Nothing here moves key bytes until the last kernel.  Every input entry gets
 // a number (the runs one after the other) and a 64-bit word: the first eight
@@ -35,6 +35,7 @@ constexpr uint32_t kGroup = kSpanLanes;      // lanes per entry in the copy (cop
 constexpr uint32_t kPutRuns = 16;            // runs per runs_put_kernel launch
 constexpr uint64_t kMaxSequence = (1ull << 56) - 1;   // LDB_MAX_SEQUENCE, dbformat.h
 constexpr uint32_t kTypeDeletion = 0;        // LDB_TYPE_DELETION
+constexpr uint32_t kTypeValue = 1;           // LDB_TYPE_VALUE: above it ldb_pkey_import fails
 
 typedef uint64_t u64_a1 __attribute__((aligned(1)));
 using bytes_g = gptr<const uint8_t>;
@@ -183,7 +184,9 @@ __global__ __launch_bounds__(256) void merge_pass_kernel(
 }
 
 // Over the final order: the drop flag of position j from entries j and j - 1
-// (db_impl.c:1369-1396), and the kept lengths.
+// (db_impl.c:1363-1397), and the kept lengths.  An entry whose type byte is
+// above 1 fails ldb_pkey_import: it is kept, and the entry behind it starts
+// over at kMaxSequence.
 __global__ __launch_bounds__(256) void neighbour_kernel(
     const MergeRun* __restrict__ table, const uint32_t* __restrict__ first,
     const uint8_t* __restrict__ erun, uint32_t n, MergeRule rule,
@@ -202,14 +205,18 @@ __global__ __launch_bounds__(256) void neighbour_kernel(
     bool drop = false;
     if (rule.drop) {
       const uint64_t tag = tag_of(k);
-      uint64_t last = kMaxSequence;                          // :1373
+      uint64_t last = kMaxSequence;                          // :1367, :1373
       if (j > 0 && kw[j - 1] == kw[j]) {
         const KeyRef q = key_of(table, first, erun, idx[j - 1], 1);
-        if (cmp_rest(q, k, 0) == 0) last = tag_of(q) >> 8;   // the same user key: :1396
+        const uint64_t qtag = tag_of(q);
+        // The same user key, and ldb_pkey_import took the entry before: :1396.
+        // Behind an unparsable one lcdb has no current user key (:1365-1367).
+        if ((uint32_t)(qtag & 0xff) <= kTypeValue && cmp_rest(q, k, 0) == 0) last = qtag >> 8;
       }
-      drop = last <= rule.smallest_snapshot ||               // (A), :1376
-             ((uint32_t)(tag & 0xff) == kTypeDeletion && (tag >> 8) <= rule.smallest_snapshot &&
-              rule.drop_deletions);                          // :1379-1382
+      drop = (uint32_t)(tag & 0xff) <= kTypeValue &&         // else "do not hide error keys", :1363
+             (last <= rule.smallest_snapshot ||              // (A), :1376
+              ((uint32_t)(tag & 0xff) == kTypeDeletion && (tag >> 8) <= rule.smallest_snapshot &&
+               rule.drop_deletions));                        // :1379-1382
     }
     keep[j] = drop ? 0u : 1u;
     klen[j] = drop ? 0u : k.len;

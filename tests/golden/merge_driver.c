@@ -26,6 +26,12 @@
  *           per operation u32 kind: 0 put (key length, key, value length,
  *           value), 1 delete (key length, key), 2 ldb_test_compact_memtable,
  *           3 ldb_snapshot, never released)
+ *        merge_driver repair DBDIR SCRIPT OUTDIR
+ *          (DBDIR holds nothing but table files <number>.ldb written by the
+ *           `build` mode: ldb_repair puts them at level 0 and sets the last
+ *           sequence to the largest parsable one in them; then `compact` as
+ *           it stands: the open, the script, the two steps and the stage
+ *           dumps.  tests/golden/make_merge_sweep_golden.py)
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -298,8 +304,11 @@ dump_stage(ldb_t *db, const char *dbdir, const char *outdir, int stage) {
   int level;
   FILE *f;
 
-  sprintf(cmd, "mkdir -p '%s/stage%d' && cp '%s'/*.ldb '%s/stage%d/'", outdir, stage, dbdir,
-          outdir, stage);
+  /* A compaction that keeps nothing leaves no table file behind. */
+  sprintf(cmd,
+          "mkdir -p '%s/stage%d' && for f in '%s'/*.ldb; do "
+          "[ -e \"$f\" ] || continue; cp \"$f\" '%s/stage%d/' || exit 1; done",
+          outdir, stage, dbdir, outdir, stage);
 
   if (system(cmd) != 0) {
     fprintf(stderr, "copy failed: %s\n", cmd);
@@ -334,7 +343,7 @@ dump_stage(ldb_t *db, const char *dbdir, const char *outdir, int stage) {
 }
 
 static int
-do_compact(const char *dbdir, const char *script, const char *outdir) {
+do_compact(int repair, const char *dbdir, const char *script, const char *outdir) {
   ldb_dbopt_t options;
   unsigned long nops, i;
   ldb_t *db;
@@ -347,6 +356,14 @@ do_compact(const char *dbdir, const char *script, const char *outdir) {
   options = *ldb_dbopt_default;
   options.create_if_missing = 1;
   options.compression = LDB_NO_COMPRESSION;
+
+  if (repair) {
+    rc = ldb_repair(dbdir, &options);
+    if (rc != LDB_OK) {
+      fprintf(stderr, "repair of %s: %s\n", dbdir, ldb_strerror(rc));
+      return 1;
+    }
+  }
 
   rc = ldb_open(dbdir, &options, &db);
   if (rc != LDB_OK) {
@@ -411,9 +428,12 @@ main(int argc, char **argv) {
     return do_merge(1, atoi(argv[2]), argv[3], argc - 4, argv + 4);
 
   if (argc == 5 && strcmp(argv[1], "compact") == 0)
-    return do_compact(argv[2], argv[3], argv[4]);
+    return do_compact(0, argv[2], argv[3], argv[4]);
 
-  fprintf(stderr, "usage: %s build | merge | --time | compact ... (see the source)\n", argv[0]);
+  if (argc == 5 && strcmp(argv[1], "repair") == 0)
+    return do_compact(1, argv[2], argv[3], argv[4]);
+
+  fprintf(stderr, "usage: %s build | merge | --time | compact | repair ... (see the source)\n", argv[0]);
 
   return 2;
 }

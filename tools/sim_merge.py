@@ -18,9 +18,13 @@ Two routes to the same order:
   tie at the rest: bytes from offset 8, the length, then (internal keys) the
   tag, descending.
 
-``drop_flags`` is db_impl.c:1369-1396 with entry i and entry i - 1 of the
+``drop_flags`` is db_impl.c:1363-1397 with entry i and entry i - 1 of the
 merged order only, as the kernel evaluates it; ``drop_serial`` is the loop as
-the reference writes it.  The tests hold each pair equal.
+the reference writes it.  The tests hold each pair equal.  A key whose type
+byte is above 1 fails ldb_pkey_import (dbformat.c:86-107): lcdb keeps such an
+entry and forgets the current user key, so the entry behind it counts as a
+first occurrence.  ldb_put cannot write one, but a compaction reads table
+files, and lcdb's repairer accepts tables that hold them.
 """
 from __future__ import annotations
 
@@ -134,28 +138,41 @@ def merge_ranks(runs, internal: bool = False):
     return groups[0] if groups else []
 
 
+def parsable(key: bytes) -> bool:
+    """ldb_pkey_import (dbformat.c:86-107) on a key of at least 8 bytes: the
+    tag's type byte is a deletion's or a value's."""
+    return key[-8] <= TYPE_VALUE
+
+
 def drop_flags(keys, smallest_snapshot: int, drop_deletions: bool):
     """Per entry of the merged order (internal keys): True = dropped.  Only
-    keys[i] and keys[i - 1] are read."""
+    keys[i] and keys[i - 1] are read: an unparsable entry is kept, and the
+    entry behind one starts over at MAX_SEQUENCE like a first occurrence."""
     out = []
     for i, k in enumerate(keys):
         last = MAX_SEQUENCE
-        if i and keys[i - 1][:-8] == k[:-8]:
+        if i and keys[i - 1][:-8] == k[:-8] and parsable(keys[i - 1]):
             last = tag_of(keys[i - 1]) >> 8
         t = tag_of(k)
-        out.append(last <= smallest_snapshot or
-                   ((t & 0xff) == TYPE_DELETION and (t >> 8) <= smallest_snapshot and
-                    bool(drop_deletions)))
+        out.append(parsable(k) and
+                   (last <= smallest_snapshot or
+                    ((t & 0xff) == TYPE_DELETION and (t >> 8) <= smallest_snapshot and
+                     bool(drop_deletions))))
     return out
 
 
 def drop_serial(keys, smallest_snapshot: int, drop_deletions: bool):
-    """db_impl.c:1369-1396 as written: one walk with its two variables."""
+    """db_impl.c:1363-1397 as written: one walk with its variables, the failed
+    ldb_pkey_import ("do not hide error keys") included."""
     out = []
-    user_key, last = None, MAX_SEQUENCE
+    user_key, has_user_key, last = b"", False, MAX_SEQUENCE
     for k in keys:
-        if user_key is None or k[:-8] != user_key:
-            user_key, last = k[:-8], MAX_SEQUENCE
+        if not parsable(k):                                   # :1363-1367
+            user_key, has_user_key, last = b"", False, MAX_SEQUENCE
+            out.append(False)
+            continue
+        if not has_user_key or k[:-8] != user_key:
+            user_key, has_user_key, last = k[:-8], True, MAX_SEQUENCE
         t = tag_of(k)
         drop = False
         if last <= smallest_snapshot:
