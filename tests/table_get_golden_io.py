@@ -143,7 +143,9 @@ def version_entries() -> list:
     """Hand-made internal-key entries no fixture table has in one block: many
     versions of one user key, whose tags share leading bytes, so that an entry's
     `shared` count reaches into the previous key's tag (dbformat.c:206-230
-    sorts the larger sequence first)."""
+    sorts the larger sequence first).  Checked against the Python model only;
+    the `versions` family of tests/read_sweep.py is what holds these shapes
+    to lcdb (tests/golden/read_sweep.bin)."""
     def ik(user, seq, typ=1):
         return user + struct.pack("<Q", (seq << 8) | typ)
     seqs = [0x060403, 0x050403, 0x050402, 0x040402, 0x030402, 0x000402, 0x000302]
