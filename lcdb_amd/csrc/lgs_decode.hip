@@ -1078,6 +1078,16 @@ __global__ __launch_bounds__(128) void decode_pair_kernel(
     order();
     if ((st == 1) & ((pub & kRej) != 0)) st = 0;
     LGS_PAIR_PH(1);
+    // The mover sets the trip (the walker waits for it at the barrier), so
+    // through the flush and the first slot it issues ahead of the walker it
+    // shares a SIMD with.  At equal priority the SIMD favours the wave in the
+    // lower wave slot: the quarter of the movers that sat in slot 1, beside a
+    // slot-0 walker, took 4 835 cycles of work a trip against 4 400 for the
+    // others, and the launch ended with them.  Back to the walker's priority
+    // for the second slot: the walker then reaches its refill requests
+    // sooner, and their loads have the barrier to land in (DESIGN 4.2,
+    // profiles/r12_*).
+    __builtin_amdgcn_s_setprio(1);
 
     // ---- flush finished bytes: whole 128-byte lines of the destination, up
     // to the last line boundary at or below dst + made, so every interior
@@ -1143,6 +1153,7 @@ __global__ __launch_bounds__(128) void decode_pair_kernel(
     slot_step(e0, pub, false);
     order();
     LGS_PAIR_PH(3);
+    __builtin_amdgcn_s_setprio(0);
     slot_step(e1, pub, true);
     order();
     LGS_PAIR_PH(4);

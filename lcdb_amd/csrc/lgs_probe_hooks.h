@@ -59,21 +59,36 @@ __device__ __forceinline__ uint32_t lgs_ring_ph_value_(const uint32_t* ph, uint3
 // At the end the mover's lanes 0-8 write its sums and trip count into their
 // blocks' out_len entries, the walker's lanes 16-24 its own, after a barrier
 // behind the mover's drained stores (both waves execute PAIR_PH_END_*).
+// Lane 9 of the mover and lane 25 of the walker write where their wave ran
+// (lgs_hw_where_: HW_ID bits 15:0 -- wave slot 3:0, SIMD 5:4, pipe 7:6, CU
+// 11:8, SH 12, SE 15:13 -- and the XCC id in bits 19:16), so
+// tools/ring_phases.py can set a workgroup's life against what shared its
+// mover's SIMD.
 #ifdef LGS_PROBE_RING_PHASES
-#define LGS_PAIR_PH_DECL LGS_RING_PH_DECL
+__device__ __forceinline__ uint32_t lgs_hw_where_() {
+  // s_getreg_b32 immediates: register | offset << 6 | (size - 1) << 11;
+  // HW_REG_HW_ID is register 4, HW_REG_XCC_ID register 20 (gfx942 / gfx950).
+  const uint32_t hw = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (15 << 11));
+  const uint32_t xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));
+  return hw | (xcc << 16);
+}
+#define LGS_PAIR_PH_DECL            \
+  LGS_RING_PH_DECL;                 \
+  const uint32_t ph_where_ = lgs_hw_where_()
 #define LGS_PAIR_PH(k) LGS_RING_PH(k)
 #define LGS_PAIR_PH_TRIP() LGS_RING_PH_TRIP()
 #define LGS_PAIR_PH_END_MOVER(ok, lane, ptr)                              \
   do {                                                                    \
-    if ((ok) && (lane) <= 8) *(ptr) = lgs_ring_ph_value_(ph_, ph_trips_, (lane), 0u); \
+    if ((ok) && (lane) <= 9)                                              \
+      *(ptr) = (lane) == 9 ? ph_where_ : lgs_ring_ph_value_(ph_, ph_trips_, (lane), 0u); \
     __builtin_amdgcn_s_waitcnt(0x0f70);                                   \
     pair_barrier();                                                       \
   } while (0)
 #define LGS_PAIR_PH_END_WALKER(ok, lane, ptr)                             \
   do {                                                                    \
     pair_barrier();                                                       \
-    if ((ok) && (lane) >= 16 && (lane) <= 24)                             \
-      *(ptr) = lgs_ring_ph_value_(ph_, ph_trips_, (lane) - 16, 0u);       \
+    if ((ok) && (lane) >= 16 && (lane) <= 25)                             \
+      *(ptr) = (lane) == 25 ? ph_where_ : lgs_ring_ph_value_(ph_, ph_trips_, (lane) - 16, 0u); \
   } while (0)
 #else
 #define LGS_PAIR_PH_DECL do {} while (0)

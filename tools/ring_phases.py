@@ -24,7 +24,9 @@ and runs the pair kernel.
 usage: python tools/ring_phases.py PROBE_SO [PRODUCT_SO]
 Prints one JSON line: per-phase cycles per wave (median over waves), per
 trip, the share of the wave's life, and the launch times of the probe and
-(if given) the product library, HIP-event timed.
+(if given) the product library, HIP-event timed.  For the pair kernel a
+table follows: mover life and trips by what else ran on the mover's SIMD
+(lane 9 of the mover and lane 25 of the walker report HW_ID and XCC_ID).
 """
 from __future__ import annotations
 
@@ -41,6 +43,62 @@ NAMES = ["piece1", "wait_vmcnt", "landing", "flush", "parse1", "slot2", "refill_
 # wait for the other role.
 PAIR_MOVER = ["wait_vmcnt", "far_landing", "flush", "slot1", "slot2", "", "", "barrier"]
 PAIR_WALKER = ["wait_vmcnt", "refill_landing", "slot1", "slot2", "end_refill_req", "", "", "barrier"]
+
+
+def placement(v) -> dict:
+    """Life against placement: v is one row of 64 out_len words per
+    walker/mover pair.  Word 9 (mover) and word 25 (walker) hold where the wave
+    ran: HW_ID bits 15:0 (wave slot 3:0, SIMD 5:4, CU 11:8, SH 12, SE 15:13)
+    and the XCC id in bits 19:16.  A pair's class is the (walkers, movers)
+    count of the SIMD its mover ran on."""
+    import collections
+    import numpy as np
+
+    def simd(w):     # (xcc, se/sh/cu, simd): one id per SIMD of the chip
+        return (w >> 16) * 4096 + ((w >> 8) & 0xff) * 4 + ((w >> 4) & 3)
+
+    mw, ww = v[:, 9], v[:, 25]
+    ms, ws = simd(mw), simd(ww)
+    nm, nw = collections.Counter(ms.tolist()), collections.Counter(ws.tolist())
+    per_simd = collections.Counter((nw.get(s, 0), nm.get(s, 0)) for s in set(nm) | set(nw))
+    cls = np.array([nw.get(s, 0) * 10 + nm.get(s, 0) for s in ms.tolist()])
+    life, trips = v[:, 0:8].sum(axis=1), v[:, 8]
+    slow = life >= np.percentile(life, 90)
+    rows = []
+    for c in sorted(set(cls.tolist())):
+        k = cls == c
+        rows.append({"class": "(%d,%d)" % (c // 10, c % 10), "pairs": int(k.sum()),
+                     "trips_p50": float(np.median(trips[k])), "trips_max": int(trips[k].max()),
+                     "life_p50": float(np.median(life[k])),
+                     "life_p90": float(np.percentile(life[k], 90)),
+                     "life_max": int(life[k].max()),
+                     "in_slowest_decile": int((k & slow).sum())})
+    # The wave slots of two waves that share a SIMD (do their low bits differ?).
+    by = collections.defaultdict(list)
+    for s, w in zip(ms.tolist() + ws.tolist(), mw.tolist() + ww.tolist()):
+        by[s].append(w & 15)
+    slots = collections.Counter(tuple(sorted(x)) for x in by.values())
+    return {"simds": len(by), "cus": len({s // 4 for s in by}),
+            "per_simd_walkers_movers": {"(%d,%d)" % k: n for k, n in sorted(per_simd.items())},
+            "slots_sharing_a_simd": {str(k): n for k, n in sorted(slots.items())},
+            "slowest_decile_pairs": int(slow.sum()),
+            "corr_life_trips": float(np.corrcoef(life, trips)[0, 1]),
+            "rows": rows}
+
+
+def placement_table(p: dict) -> str:
+    out = ["# mover life by what shares the mover's SIMD, class = (walkers, movers) on it",
+           "# SIMDs %d  CUs %d  per-SIMD (walkers, movers): %s" % (
+               p["simds"], p["cus"], p["per_simd_walkers_movers"]),
+           "# wave slots of the waves sharing a SIMD: %s" % p["slots_sharing_a_simd"],
+           "# slowest decile: %d pairs; corr(life, trips) = %.3f" % (
+               p["slowest_decile_pairs"], p["corr_life_trips"]),
+           "class   pairs  trips_p50  trips_max   life_p50   life_p90   life_max  in_slowest_decile"]
+    for r in p["rows"]:
+        out.append("%-6s %6d %10.0f %10d %10.0f %10.0f %10d %10d" % (
+            r["class"], r["pairs"], r["trips_p50"], r["trips_max"], r["life_p50"], r["life_p90"],
+            r["life_max"], r["in_slowest_decile"]))
+    return "\n".join(out)
 
 
 def child(lib: str, phases: bool) -> dict:
@@ -82,6 +140,10 @@ def child(lib: str, phases: bool) -> dict:
                 "phase_cycles_per_trip": {n: round(float(x) / t50, 1)
                                           for n, x in zip(names, med) if n},
                 "work_cycles_per_trip": round(float(med[:7].sum()) / t50, 1)}
+        words = out.len.cpu().numpy().astype(np.int64).reshape(-1, 64)
+        res["placement"] = placement(words)
+        if os.environ.get("RING_PHASES_DUMP"):     # the raw words, for a closer look
+            np.save(os.environ["RING_PHASES_DUMP"], words)
     elif phases:
         v = out.len.cpu().numpy().astype(np.float64).reshape(-1, 32)   # 32 blocks per wave
         ph = v[:, :8]
@@ -112,6 +174,8 @@ def main() -> None:
         d = json.loads(line)
         out["probe" if ph == "1" else "product"] = d
     print(json.dumps(out))
+    if "placement" in out.get("probe", {}):
+        print(placement_table(out["probe"]["placement"]))
 
 
 if __name__ == "__main__":
