@@ -22,10 +22,10 @@ import re
 import subprocess
 import sys
 
-import numpy as np
 import pytest
 
 import oracle
+from encode_helpers import _copies, _device_batch, _other, _probe_offsets, _rnd
 from lcdb_amd import corpus
 
 pytestmark = pytest.mark.gpu
@@ -35,27 +35,6 @@ PROBE = os.environ.get("LGS_TEST_PROBE") == "1"
 
 SIZES = [17, 18, 255, 256, 257, 2047, 2048, 2049, 4096, 4208, 16384, 65536, 65536 + 17,
          65536 + 16, 131072 + 100]
-
-
-def _probe_offsets(count: int) -> list[int]:
-    """snappy.c:138-143: offset of the search's probe k from its first."""
-    offs, at, skip = [], 0, 32
-    for _ in range(count):
-        offs.append(at)
-        step = skip >> 5
-        skip += step
-        at += step
-    return offs
-
-
-def _rnd(rng: random.Random, n: int, avoid: bytes = b"") -> bytes:
-    """n random bytes, none of them zero or in `avoid`."""
-    alpha = [b for b in range(1, 256) if b not in avoid]
-    return bytes(rng.choice(alpha) for _ in range(n))
-
-
-def _other(rng: random.Random, *not_these: int) -> bytes:
-    return bytes([rng.choice([b for b in range(1, 256) if b not in not_these])])
 
 
 def _mixed(rng: random.Random, n: int) -> bytes:
@@ -215,32 +194,6 @@ def _cases() -> list[tuple[str, bytes]]:
     return cases
 
 
-def _copies(stream: bytes) -> list[int]:
-    """Lengths of the copy elements of a Snappy stream."""
-    at, out = 0, []
-    while stream[at] & 0x80:
-        at += 1
-    at += 1
-    while at < len(stream):
-        tag = stream[at]
-        kind = tag & 3
-        if kind == 0:
-            ln = tag >> 2
-            at += 1
-            if ln >= 60:
-                nb = ln - 59
-                ln = int.from_bytes(stream[at:at + nb], "little")
-                at += nb
-            at += ln + 1
-        elif kind == 1:
-            out.append(((tag >> 2) & 7) + 4)
-            at += 2
-        else:
-            out.append((tag >> 2) + 1)
-            at += 3 if kind == 2 else 5
-    return out
-
-
 CASES = _cases()
 
 
@@ -276,22 +229,6 @@ def _check(outs, names, expected, route):
         assert o == expected[name], (route, name)
     for name, o in zip(names[:8], outs[:8]):
         assert ref.decode(o) is not None, (route, name)
-
-
-def _device_batch(blocks: list[bytes]) -> list[bytes]:
-    import torch
-    from lcdb_amd import batch
-    parts = []
-    for b in blocks:
-        a = np.frombuffer(b, dtype=np.uint8)
-        parts.append(corpus.Corpus(np.concatenate([a, np.zeros(16, np.uint8)]),
-                                   np.zeros(1, np.uint64), np.array([len(b)], np.uint32)))
-    c = corpus.concat(*parts)
-    raw = batch.upload(c)
-    comp = batch.encode_slots(raw)
-    batch.encode(raw, comp)
-    torch.cuda.synchronize()
-    return batch.to_host(comp).blocks()
 
 
 def _launches():
