@@ -10,62 +10,12 @@ import numpy as np
 import pytest
 
 import oracle
+from decode_helpers import Stream, _header, _varint  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 CAP = 4608
 COUNTS = (1, 2, 63, 64, 65, 128, 129, 193)
-
-
-# ---- stream building (snappy.c:53-110 tag forms) ---------------------------
-def _varint(n: int) -> bytes:
-    out = bytearray()
-    while n >= 0x80:
-        out.append((n & 0x7F) | 0x80)
-        n >>= 7
-    out.append(n)
-    return bytes(out)
-
-
-class Stream:
-    """A Snappy body grown op by op, with the output it decodes to."""
-
-    def __init__(self, rng):
-        self.rng, self.body, self.out = rng, bytearray(), bytearray()
-
-    def lit(self, n: int) -> "Stream":
-        b = self.rng.randbytes(n)
-        m = n - 1
-        if m < 60:
-            self.body.append(m << 2)
-        elif m < 256:
-            self.body += bytes([60 << 2, m])
-        else:
-            self.body += bytes([61 << 2, m & 255, m >> 8])
-        self.body += b
-        self.out += b
-        return self
-
-    def copy(self, n: int, d: int, form: int = 2) -> "Stream":
-        assert 1 <= n <= 64 and 1 <= d <= len(self.out)
-        if form == 1:
-            assert 4 <= n <= 11 and d < 2048
-            self.body += bytes([((d >> 8) << 5) | ((n - 4) << 2) | 1, d & 255])
-        elif form == 2:
-            self.body += bytes([((n - 1) << 2) | 2, d & 255, d >> 8])
-        else:
-            self.body += bytes([((n - 1) << 2) | 3]) + d.to_bytes(4, "little")
-        for _ in range(n):
-            self.out.append(self.out[-d])
-        return self
-
-    def pos(self) -> int:
-        """Stream offset of the next tag (the header is 1 byte below 128
-        output bytes and 2 bytes from there to 16 383)."""
-        return len(self.body)
-
-    def done(self, want: int | None = None) -> bytes:
-        return _varint(len(self.out) if want is None else want) + bytes(self.body)
 
 
 ONE_TAG = _varint(5) + bytes([4 << 2]) + b"hello"
@@ -247,15 +197,6 @@ def _expected(s: bytes):
     if s not in _REF:
         _REF[s] = oracle.best().decode(s) if s else None
     return _REF[s]
-
-
-def _header(s: bytes):
-    v = 0
-    for k in range(min(5, len(s))):
-        v |= (s[k] & 0x7F) << (7 * k)
-        if not s[k] & 0x80:
-            return v if v <= 0x7FFFFFFF else None
-    return None
 
 
 def _check(gpu, streams, cap: int = CAP) -> int:

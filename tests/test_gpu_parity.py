@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import oracle
+from decode_helpers import _copy2, _lit
 from lcdb_amd import corpus
 
 pytestmark = pytest.mark.gpu
@@ -627,22 +628,6 @@ def test_hbm_copy_probe_exact_and_rejects_misaligned(gpu):
         assert torch.equal(dst[:nbytes], src[:nbytes]), nbytes
         assert int(dst[nbytes:].count_nonzero()) == 0, nbytes   # nothing past the end
     assert lib.lgs_hbm_copy_dev(dst.data_ptr(), src.data_ptr(), 24, None) != 0
-
-
-def _lit(b: bytes) -> bytes:
-    # literal tag, snappy.c:53-73 header forms (1-3 length bytes here)
-    n = len(b) - 1
-    if n < 60:
-        return bytes([n << 2]) + b
-    if n < 256:
-        return bytes([60 << 2, n]) + b
-    if n < 65536:
-        return bytes([61 << 2, n & 255, n >> 8]) + b
-    return bytes([62 << 2, n & 255, (n >> 8) & 255, n >> 16]) + b
-
-
-def _copy2(length: int, dist: int) -> bytes:
-    return bytes([((length - 1) << 2) | 2, dist & 255, dist >> 8])
 
 
 @pytest.mark.parametrize("wide", _with_probe(["walk"], ["trips"]))
