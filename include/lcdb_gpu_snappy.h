@@ -438,6 +438,41 @@ int lgs_tables_build_dev(const uint8_t *d_keys, const uint64_t *d_key_off,
                          uint32_t *d_file_first, uint32_t files_cap_count, uint32_t *n_files,
                          uint64_t *files_bytes, void *stream);
 
+/* The cut and the build with forced starts: a compaction closes
+   its output file before a key when ldb_compaction_should_stop_before says so
+   (db_impl.c:1354-1360), and ldb_finish_compaction_output_file flushes the
+   pending block, so such a file start is a block start that the size rule did
+   not choose.  d_forced: n uint32 flags in device memory as
+   lgs_merge_stops_dev writes them, or NULL; entry i > 0 with a nonzero flag
+   starts a block and a file (flag 0 is ignored: entry 0 starts both anyway).
+   The block that starts at s ends at the size rule's place or before the
+   first forced start behind s, whichever comes first; a file that starts at
+   block s ends after the first block that reaches max_file_size or before
+   the next block whose first entry is forced.  Everything else is
+   lgs_block_cut_dev and lgs_tables_build_dev, which are the NULL case of
+   these calls.  lgs_tables_build_forced_bound counts n_forced (the number of
+   nonzero flags, lgs_merge_plan_version_dev's d_counts[6]) more files. */
+int lgs_block_cut_forced_dev(const uint8_t *d_keys, const uint64_t *d_key_off,
+                             const uint32_t *d_key_len, const uint32_t *d_val_len, uint32_t n,
+                             uint64_t block_size, uint32_t restart_interval, int internal_keys,
+                             const uint32_t *d_forced, uint32_t *d_block_first,
+                             uint64_t *d_raw_off, uint32_t *d_raw_len, uint64_t *d_ikey_off,
+                             uint64_t *d_counts, void *d_scratch, size_t scratch_bytes,
+                             void *stream);
+size_t lgs_tables_build_forced_bound(uint32_t n, uint64_t key_bytes, uint64_t value_bytes,
+                                     int bits_per_key, uint64_t max_file_size, uint32_t n_forced,
+                                     uint32_t *max_files);
+int lgs_tables_build_forced_dev(const uint8_t *d_keys, const uint64_t *d_key_off,
+                                const uint32_t *d_key_len, const uint8_t *d_vals,
+                                const uint64_t *d_val_off, const uint32_t *d_val_len, uint32_t n,
+                                uint64_t key_bytes, uint64_t value_bytes, uint64_t block_size,
+                                uint32_t restart_interval, int compression, int bits_per_key,
+                                int internal_keys, uint64_t max_file_size,
+                                const uint32_t *d_forced, uint8_t *d_files, size_t files_cap,
+                                uint64_t *d_file_off, uint64_t *d_file_size,
+                                uint32_t *d_file_first, uint32_t files_cap_count,
+                                uint32_t *n_files, uint64_t *files_bytes, void *stream);
+
 /* ---- batched point lookups ----
  *
  * ldb_blockiter_create + one ldb_blockiter_seek on the fresh iterator
@@ -743,8 +778,9 @@ int lgs_table_scan_dev(lgs_table *table, int verify_checksums, const uint8_t *st
  * is the comparator's, by the raw tag, whatever the type byte.
  * drop_deletions stands for
  * ldb_compaction_is_base_level_for_key, which the caller asserts for the
- * whole call: a caller whose answer differs by key range splits the merge by
- * range.  With drop = 0 nothing is dropped, and smallest_snapshot and
+ * whole call: a caller whose answer differs by key gives the levels below
+ * the output to lgs_merge_plan_version_dev (below), which answers per key.
+ * With drop = 0 nothing is dropped, and smallest_snapshot and
  * drop_deletions are ignored.
  *
  * Two device calls, as lgs_block_cut_dev / _emit_dev, because the host sizes
@@ -791,6 +827,60 @@ int lgs_merge_host(const lgs_run *runs, uint32_t nruns, int internal_keys, int d
                    uint64_t *key_off, uint32_t *key_len, uint8_t *vals, size_t val_cap,
                    uint64_t *val_off, uint32_t *val_len, uint32_t *src_run, uint32_t *src_index,
                    uint32_t entry_cap, uint64_t *needed);
+
+/* The same plan for a compaction inside a version: the two
+ * pieces of ldb_do_compaction_work's loop (db_impl.c:1352-1425) that depend on
+ * the levels below the output.  Internal keys and the drop rule are implied.
+ *
+ * levels: a host array of nlevels <= LGS_VERSION_MAX_LEVELS file lists, levels
+ * output + 1 (the compaction's level + 2) to 6 in that order; all of it, keys
+ * included, is host memory and is copied before the call returns.  Within a
+ * level the files are in the level's order: disjoint, `largest` strictly
+ * increasing under the internal comparator.  Every key has at least 8 bytes
+ * and a level has under 2^31 files (else LGS_EINVAL, as for nlevels above the
+ * maximum).  nlevels = 0: no stops, every key at base level, which is
+ * lgs_merge_plan_dev(internal_keys = 1, drop = 1, drop_deletions = 1).
+ *
+ * Base level: where the drop rule above reads drop_deletions, this plan reads
+ * ldb_compaction_is_base_level_for_key (version_set.c:2289-2321) of the
+ * entry's user key: in every level the first file whose largest user key is
+ * >= the key does not exist or has a smallest user key above it.
+ *
+ * Stops: ldb_compaction_should_stop_before (version_set.c:2324-2351) runs
+ * before every entry of the merged order, kept or not, against levels[0] with
+ * limit max_grandparent_overlap (file sizes sum to under 2^63: the caller's
+ * contract, lcdb's overlapped_bytes is an int64_t).  Files passed by the first
+ * key cost nothing.  A stop closes the output file only when one is open, so
+ * kept entry k > 0 is a forced file start exactly when a stop lies behind the
+ * position of kept entry k - 1 and not behind its own.  d_counts[6] is the
+ * number of forced starts; lgs_merge_stops_dev, after the plan and with the
+ * same scratch, writes the n_out = d_counts[0] flags (uint32, flag 0 is 0) for
+ * lgs_tables_build_forced_dev.  lgs_merge_emit_dev is used as it is, with
+ * this plan's scratch.
+ *
+ * lgs_merge_version_scratch(n_total, nruns, files in all levels, bytes of
+ * all their keys) sizes the scratch.  The plan synchronises `stream` before it
+ * returns (the levels are uploaded from the caller's memory). */
+typedef struct lgs_level_file {
+  const uint8_t *smallest;
+  uint32_t smallest_len;
+  const uint8_t *largest;
+  uint32_t largest_len;
+  uint64_t file_size;
+} lgs_level_file;
+typedef struct lgs_level {
+  const lgs_level_file *files;
+  uint32_t n;
+} lgs_level;
+#define LGS_VERSION_MAX_LEVELS 5
+size_t lgs_merge_version_scratch(uint32_t n_total, uint32_t nruns, uint64_t level_files,
+                                 uint64_t level_key_bytes);
+int lgs_merge_plan_version_dev(const lgs_run *runs, uint32_t nruns, uint64_t smallest_snapshot,
+                               const lgs_level *levels, uint32_t nlevels,
+                               uint64_t max_grandparent_overlap, uint64_t *d_counts,
+                               void *d_scratch, size_t scratch_bytes, void *stream);
+int lgs_merge_stops_dev(uint32_t n_total, uint32_t n_out, uint32_t *d_forced,
+                        const void *d_scratch, size_t scratch_bytes, void *stream);
 
 /* Devices and diagnostics. */
 /* The drop-in's current footprint: pinned and device bytes held by its

@@ -84,6 +84,16 @@ _SIGS = {
                                        C.c_int, C.c_uint64, _vp, C.c_size_t, _vp, _vp, _vp,
                                        C.c_uint32, C.POINTER(C.c_uint32),
                                        C.POINTER(C.c_uint64), _vp]),
+    "lgs_block_cut_forced_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint32,
+                                           C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
+                                           _vp]),
+    "lgs_tables_build_forced_bound": (C.c_size_t, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_int,
+                                                   C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "lgs_tables_build_forced_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64,
+                                              C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_int,
+                                              C.c_int, C.c_uint64, _vp, _vp, C.c_size_t, _vp, _vp,
+                                              _vp, C.c_uint32, C.POINTER(C.c_uint32),
+                                              C.POINTER(C.c_uint64), _vp]),
     "lgs_block_seek_scratch": (C.c_size_t, [C.c_uint32]),
     "lgs_block_seek_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32,
                                      C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -127,6 +137,10 @@ _SIGS = {
     "lgs_merge_host": (C.c_int, [_vp, C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.c_int, _vp,
                                  C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp,
                                  C.c_uint32, _vp]),
+    "lgs_merge_version_scratch": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]),
+    "lgs_merge_plan_version_dev": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _vp, C.c_uint32,
+                                             C.c_uint64, _vp, _vp, C.c_size_t, _vp]),
+    "lgs_merge_stops_dev": (C.c_int, [C.c_uint32, C.c_uint32, _vp, _vp, C.c_size_t, _vp]),
     "lgs_dropin_footprint": (C.c_int, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                        C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]),
     "lgs_service_quiesce": (C.c_int, []),
@@ -147,6 +161,19 @@ class LgsRun(C.Structure):
     _fields_ = [("keys", _vp), ("key_off", _vp), ("key_len", _vp), ("vals", _vp),
                 ("val_off", _vp), ("val_len", _vp), ("n", C.c_uint32)]
 
+
+class LgsLevelFile(C.Structure):
+    """lgs_level_file: one file of a level below a compaction's output."""
+    _fields_ = [("smallest", _vp), ("smallest_len", C.c_uint32), ("largest", _vp),
+                ("largest_len", C.c_uint32), ("file_size", C.c_uint64)]
+
+
+class LgsLevel(C.Structure):
+    """lgs_level: one level's files, in the level's order (host memory)."""
+    _fields_ = [("files", C.POINTER(LgsLevelFile)), ("n", C.c_uint32)]
+
+
+LGS_VERSION_MAX_LEVELS = 5
 
 # Every symbol include/lcdb_gpu_snappy.h declares.
 EXPORTED = tuple(_SIGS)

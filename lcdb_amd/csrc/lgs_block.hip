@@ -23,6 +23,10 @@
 // Compaction's output files (tools/sim_table_split.py) are
 // steps 3 and 4 again over the framed blocks: a file ends after the first
 // block that takes it to max_output_file_size (db_impl.c:1417-1425).
+// Forced starts: an entry before which compaction closed its
+// output file (ldb_compaction_should_stop_before) starts a block and a file
+// whatever the sizes say; both searches then stop at the first forced index
+// behind their start (first_forced), and nothing else changes.
 #include "lgs_block.h"
 #include "lgs_device.h"
 
@@ -103,9 +107,27 @@ __device__ __forceinline__ uint64_t estimate(const uint64_t* __restrict__ S,
   return S[j + 1] - S[s] + C[s + q * R] - (s >= R ? C[s - R] : 0) + 4ull * (q + 1) + 4;
 }
 
+// The first index in (s, e) whose forced flag is set, e when there is none:
+// F is the flags' exclusive scan (F[i] = the flags before i, F[n] their sum),
+// so the flags in [s + 1, j] number F[j + 1] - F[s + 1].  s < e <= n.
+__device__ __forceinline__ uint32_t first_forced(const uint64_t* __restrict__ F, uint32_t s,
+                                                 uint32_t e) {
+  const uint64_t base = F[s + 1];
+  if (F[e] == base) return e;
+  uint32_t lo = s + 1, hi = e - 1;
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (F[mid + 1] > base) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo;
+}
+
+template <bool kForced>
 __global__ __launch_bounds__(256) void next_kernel(const uint64_t* __restrict__ S,
                                                    const uint64_t* __restrict__ C,
                                                    uint64_t block_size, uint32_t R,
+                                                   const uint64_t* __restrict__ F,
                                                    uint32_t* __restrict__ next, uint32_t n) {
   const uint32_t s = blockIdx.x * 256 + threadIdx.x;
   if (s >= n) return;
@@ -127,7 +149,8 @@ __global__ __launch_bounds__(256) void next_kernel(const uint64_t* __restrict__ 
     if (estimate(S, C, R, s, mid) >= block_size) hi = mid;
     else lo = mid + 1;
   }
-  next[s] = lo < n ? lo + 1 : n;
+  const uint32_t e = lo < n ? lo + 1 : n;
+  next[s] = kForced ? first_forced(F, s, e) : e;
 }
 
 // ---- step 4: one round of pointer doubling --------------------------------
@@ -319,9 +342,20 @@ __device__ __forceinline__ uint64_t framed_end(const uint64_t* __restrict__ hoff
   return hoff[b] + hsize[b] + 5;                     // contents, type, crc (table_builder.c:150)
 }
 
+// Per block: the forced flag of its first entry.
+__global__ __launch_bounds__(256) void block_flags_kernel(const uint32_t* __restrict__ forced,
+                                                          const uint32_t* __restrict__ block_first,
+                                                          uint32_t* __restrict__ fflag,
+                                                          uint32_t nb) {
+  const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+  if (b < nb) fflag[b] = forced[block_first[b]] ? 1u : 0u;
+}
+
+template <bool kForced>
 __global__ __launch_bounds__(256) void file_next_kernel(const uint64_t* __restrict__ hoff,
                                                         const uint64_t* __restrict__ hsize,
                                                         uint64_t max_size,
+                                                        const uint64_t* __restrict__ F,
                                                         uint32_t* __restrict__ next,
                                                         uint32_t* __restrict__ mark, uint32_t nb) {
   const uint32_t s = blockIdx.x * 256 + threadIdx.x;
@@ -343,7 +377,8 @@ __global__ __launch_bounds__(256) void file_next_kernel(const uint64_t* __restri
     if (framed_end(hoff, hsize, mid) - start >= max_size) hi = mid;
     else lo = mid + 1;
   }
-  next[s] = lo < nb ? lo + 1 : nb;
+  const uint32_t e = lo < nb ? lo + 1 : nb;
+  next[s] = kForced ? first_forced(F, s, e) : e;
   mark[s] = s == 0 ? 1u : 0u;
 }
 
@@ -451,7 +486,8 @@ int block_c_final(uint32_t n, uint32_t R) {
 }
 
 hipError_t launch_block_cut(const BlockIn& in, uint64_t block_size, uint32_t R, uint32_t trim,
-                            const BlockScratch& w, const BlockCut& out, hipStream_t s) {
+                            const uint32_t* forced, const BlockScratch& w, const BlockCut& out,
+                            hipStream_t s) {
   const uint32_t n = in.n;
   hipError_t e = hipMemsetAsync(out.counts, 0, 8 * kBlockCounts, s);
   if (e != hipSuccess) return e;
@@ -470,7 +506,13 @@ hipError_t launch_block_cut(const BlockIn& in, uint64_t block_size, uint32_t R, 
     c = c2;
     c2 = x;
   }
-  hipLaunchKernelGGL(next_kernel, g, t, 0, s, w.S, c, block_size, R, w.next, n);
+  if (forced) {
+    if ((e = launch_scan(2, nullptr, forced, w.part, 0, w.fs, w.fs + n, n, s)) != hipSuccess)
+      return e;
+    hipLaunchKernelGGL(next_kernel<true>, g, t, 0, s, w.S, c, block_size, R, w.fs, w.next, n);
+  } else {
+    hipLaunchKernelGGL(next_kernel<false>, g, t, 0, s, w.S, c, block_size, R, nullptr, w.next, n);
+  }
   // ceil(log2(n)) rounds reach the n-th block of a chain of single entries.
   const uint32_t* jin = w.next;
   uint32_t* jout = w.ja;
@@ -533,11 +575,21 @@ hipError_t launch_handle_values(const uint64_t* hoff, const uint64_t* hsize,
 }
 
 hipError_t launch_file_plan(const BlockIn& in, uint32_t trim, uint32_t nb, const uint64_t* hoff,
-                            const uint64_t* hsize, uint64_t max_size, const BlockScratch& w,
-                            const BlockCut& cut, const FilePlan& p, hipStream_t s) {
+                            const uint64_t* hsize, uint64_t max_size, const uint32_t* forced,
+                            const BlockScratch& w, const BlockCut& cut, const FilePlan& p,
+                            hipStream_t s) {
   if (nb == 0) return hipSuccess;
   const dim3 g(grid256(nb)), t(256);
-  hipLaunchKernelGGL(file_next_kernel, g, t, 0, s, hoff, hsize, max_size, p.next, p.mark, nb);
+  if (forced) {
+    hipLaunchKernelGGL(block_flags_kernel, g, t, 0, s, forced, cut.block_first, p.fflag, nb);
+    const hipError_t fe = launch_scan(2, nullptr, p.fflag, w.part, 0, p.ffs, p.ffs + nb, nb, s);
+    if (fe != hipSuccess) return fe;
+    hipLaunchKernelGGL(file_next_kernel<true>, g, t, 0, s, hoff, hsize, max_size, p.ffs, p.next,
+                       p.mark, nb);
+  } else {
+    hipLaunchKernelGGL(file_next_kernel<false>, g, t, 0, s, hoff, hsize, max_size, nullptr, p.next,
+                       p.mark, nb);
+  }
   // ceil(log2(nb)) rounds reach the nb-th file of a chain of single blocks.
   const uint32_t* jin = p.next;
   uint32_t* jout = p.ja;

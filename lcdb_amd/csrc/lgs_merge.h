@@ -10,7 +10,9 @@ namespace lgs {
 
 constexpr uint32_t kMergeMaxRuns = 64;
 constexpr uint32_t kMergeCounts = 8;   // {kept, key bytes, value bytes, longest key, dropped,
-                                       //  first bad run or ~0, 0, 0}
+                                       //  first bad run or ~0, forced starts (the version
+                                       //  plan, else 0), 0}
+constexpr uint32_t kVersionMaxLevels = 5;   // levels L + 2 .. 6 of a compaction at level L
 
 // One run as the kernels see it: lgs_run plus the number of entries before it.
 struct MergeRun {
@@ -40,10 +42,42 @@ struct MergeRule {
   uint64_t smallest_snapshot;
 };
 
+// The files of the levels below a compaction's output, in
+// device memory: file f's smallest and largest internal keys are the s_len /
+// l_len bytes at keys + s_off / l_off (keys readable 16 bytes past its end);
+// level v is files [first[v], first[v + 1]).  Level 0 of the list is level + 2,
+// the grandparents: P is the exclusive prefix sum of its file sizes (its
+// count + 1 values), limit is max_grandparent_overlap_bytes.
+struct VersionFile {
+  uint64_t s_off, l_off;
+  uint32_t s_len, l_len;
+};
+struct VersionDev {
+  const uint8_t* keys; const VersionFile* files; const uint64_t* P;
+  uint32_t first[kVersionMaxLevels + 1]; uint32_t nlevels;
+  uint64_t limit;
+};
+// Device scratch of the stops, per position of the final order: pg =
+// P[files of level + 2 passed by the key], the stop chain's next / ja / jb /
+// mark (lgs_block.hip's steps 3 and 4), the marks' scan sid (n + 1); per kept
+// entry: cnt, the stops up to and with it, and forced.  part: launch_scan's.
+struct VersionScratch {
+  uint64_t* pg; uint32_t* next; uint32_t* ja; uint32_t* jb; uint32_t* mark; uint64_t* sid;
+  uint32_t* cnt; uint32_t* forced; uint64_t* part;
+};
+
 // runs: host array, `first` filled in.  counts: kMergeCounts u64.
 hipError_t launch_merge_plan(const MergeRun* runs, uint32_t nruns, uint32_t n,
                              const MergeRule& rule, const MergeScratch& w, uint64_t* counts,
                              hipStream_t s);
+// The plan inside a version: internal keys and the drop rule, with
+// ldb_compaction_is_base_level_for_key per entry in place of
+// rule.drop_deletions, and ldb_compaction_should_stop_before's stops folded
+// onto the kept entries (x.forced, counts[6]).
+hipError_t launch_merge_plan_version(const MergeRun* runs, uint32_t nruns, uint32_t n,
+                                     const MergeRule& rule, const MergeScratch& w,
+                                     const VersionDev& v, const VersionScratch& x,
+                                     uint64_t* counts, hipStream_t s);
 // The kept entries to their places, from the scratch the plan left; key_off
 // and val_off get n_out + 1 values.
 hipError_t launch_merge_emit(uint32_t n, uint32_t n_out, const MergeScratch& w, uint8_t* keys,

@@ -20,6 +20,13 @@
 // three prefix scans (launch_scan) turn the keep flags and the kept lengths
 // into output positions, and the emit copies keys and values with 16 lanes
 // per entry, as lgs_scan.hip's, from loads that do not depend on one another.
+//
+// Inside a version (tools/sim_compact_version.py) the plan also
+// takes the files of the levels below the output: the drop rule asks
+// ldb_compaction_is_base_level_for_key per entry, a bisection per level, and
+// ldb_compaction_should_stop_before's stops over the pre-drop order are a
+// bisection per entry and a chain from entry 0 by pointer doubling, folded
+// onto the kept entries as forced file starts for lgs_block.hip's cut.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -118,6 +125,37 @@ __device__ __forceinline__ int cmp_rest(const KeyRef& a, const KeyRef& b, uint32
   return 0;
 }
 
+__device__ __forceinline__ int cmp_keys(const KeyRef& a, const KeyRef& b, uint32_t internal) {
+  const uint64_t wa = word_at(a.p, a.ulen), wb = word_at(b.p, b.ulen);
+  if (wa != wb) return wa < wb ? -1 : 1;
+  return cmp_rest(a, b, internal);
+}
+
+// ---- the levels below the output ---------------------------
+
+__device__ __forceinline__ KeyRef file_key(const VersionDev& v, uint32_t f, bool largest) {
+  const VersionFile& m = v.files[f];
+  const uint32_t len = largest ? m.l_len : m.s_len;
+  return KeyRef{to_global(v.keys) + (largest ? m.l_off : m.s_off), len, len - 8};
+}
+
+// ldb_compaction_is_base_level_for_key (version_set.c:2289-2321) as a pure
+// function of the user key: per level the first file whose largest user key
+// is >= the key, by bisection, must not exist or must start behind the key.
+__device__ __forceinline__ bool base_level(const VersionDev& v, const KeyRef& k) {
+  for (uint32_t lv = 0; lv < v.nlevels; ++lv) {
+    uint32_t lo = v.first[lv];
+    const uint32_t end = v.first[lv + 1];
+    uint32_t hi = end;
+    while (lo < hi) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (cmp_keys(file_key(v, mid, true), k, 0) >= 0) hi = mid; else lo = mid + 1;
+    }
+    if (lo < end && cmp_keys(file_key(v, lo, false), k, 0) <= 0) return false;
+  }
+  return true;
+}
+
 // Per input entry: its word, its number and its run; and the preconditions by
 // a compare with the entry before it in its run.
 __global__ __launch_bounds__(256) void words_kernel(const MergeRun* __restrict__ table,
@@ -186,10 +224,12 @@ __global__ __launch_bounds__(256) void merge_pass_kernel(
 // Over the final order: the drop flag of position j from entries j and j - 1
 // (db_impl.c:1363-1397), and the kept lengths.  An entry whose type byte is
 // above 1 fails ldb_pkey_import: it is kept, and the entry behind it starts
-// over at kMaxSequence.
+// over at kMaxSequence.  kVersion: base_level(v, key) stands where
+// rule.drop_deletions does.
+template <bool kVersion>
 __global__ __launch_bounds__(256) void neighbour_kernel(
     const MergeRun* __restrict__ table, const uint32_t* __restrict__ first,
-    const uint8_t* __restrict__ erun, uint32_t n, MergeRule rule,
+    const uint8_t* __restrict__ erun, uint32_t n, MergeRule rule, VersionDev v,
     const uint64_t* __restrict__ kw, const uint32_t* __restrict__ idx,
     uint32_t* __restrict__ keep, uint32_t* __restrict__ klen, uint32_t* __restrict__ vlen,
     uint64_t* __restrict__ ksrc, uint64_t* __restrict__ vsrc, uint64_t* __restrict__ from,
@@ -216,7 +256,7 @@ __global__ __launch_bounds__(256) void neighbour_kernel(
       drop = (uint32_t)(tag & 0xff) <= kTypeValue &&         // else "do not hide error keys", :1363
              (last <= rule.smallest_snapshot ||              // (A), :1376
               ((uint32_t)(tag & 0xff) == kTypeDeletion && (tag >> 8) <= rule.smallest_snapshot &&
-               rule.drop_deletions));                        // :1379-1382
+               (kVersion ? base_level(v, k) : rule.drop_deletions != 0)));   // :1379-1382
     }
     keep[j] = drop ? 0u : 1u;
     klen[j] = drop ? 0u : k.len;
@@ -238,6 +278,87 @@ __global__ void plan_finish_kernel(const uint64_t* __restrict__ tot, uint32_t n,
   counts[1] = tot[1];
   counts[2] = tot[2];
   counts[4] = n - tot[0];
+}
+
+// ---- ldb_compaction_should_stop_before over the final order (§4.10) -------
+// overlapped_bytes before position i is pg[i] less pg at the last stop (or at
+// position 0, whose passed files cost nothing: seen_key, version_set.c:2337),
+// so the stop behind i is a search and the stops are a chain from position 0.
+
+// pg[j] = P[files of level + 2 whose largest key is < key j], by the raw tag.
+__global__ __launch_bounds__(256) void passed_kernel(
+    const MergeRun* __restrict__ table, const uint32_t* __restrict__ first,
+    const uint8_t* __restrict__ erun, uint32_t n, VersionDev v, const uint32_t* __restrict__ idx,
+    uint64_t* __restrict__ pg, uint32_t* __restrict__ mark) {
+  const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const KeyRef k = key_of(table, first, erun, idx[j], 1);
+  uint32_t lo = 0, hi = v.first[1];
+  while (lo < hi) {                                  // version_set.c:2331-2335
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (cmp_keys(file_key(v, mid, true), k, 1) >= 0) hi = mid; else lo = mid + 1;
+  }
+  pg[j] = v.P[lo];
+  mark[j] = j == 0 ? 1u : 0u;
+}
+
+// The first position behind i whose overlap since i is over the limit; n when
+// there is none.  pg does not decrease.
+__global__ __launch_bounds__(256) void stop_next_kernel(const uint64_t* __restrict__ pg,
+                                                        uint64_t limit,
+                                                        uint32_t* __restrict__ next, uint32_t n) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t base = pg[i];
+  uint32_t lo = i + 1, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (pg[mid] - base > limit) hi = mid; else lo = mid + 1;   // :2343
+  }
+  next[i] = lo;
+}
+
+// One round of pointer doubling (lgs_block.hip's jump_kernel).
+__global__ __launch_bounds__(256) void stop_jump_kernel(uint32_t* mark,
+                                                        const uint32_t* __restrict__ jin,
+                                                        uint32_t* __restrict__ jout, uint32_t n) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t j = jin[i];
+  if (j < n && mark[i]) mark[j] = 1u;
+  jout[i] = j < n ? jin[j] : n;
+}
+
+// Per kept entry: the stops at positions up to and with its own (sid: the
+// exclusive scan of the marks, position 0's cleared).
+__global__ __launch_bounds__(256) void stop_fold_kernel(
+    uint32_t n, const uint32_t* __restrict__ keep, const uint64_t* __restrict__ pos,
+    const uint32_t* __restrict__ mark, const uint64_t* __restrict__ sid,
+    uint32_t* __restrict__ cnt) {
+  const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n || !keep[j]) return;
+  cnt[pos[j]] = (uint32_t)sid[j] + mark[j];
+}
+
+// Kept entry k > 0 starts a file when a stop lies behind kept entry k - 1 and
+// not behind k itself: the builder is open then (db_impl.c:1354-1360).  A stop
+// up to the first kept entry finds no builder.
+__global__ __launch_bounds__(256) void forced_kernel(const uint64_t* __restrict__ tot,
+                                                     const uint32_t* __restrict__ cnt,
+                                                     uint32_t* __restrict__ forced,
+                                                     uint64_t* __restrict__ counts) {
+  __shared__ uint32_t s_sum;
+  if (threadIdx.x == 0) s_sum = 0;
+  __syncthreads();
+  const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+  if (k < tot[0]) {
+    const uint32_t f = k > 0 && cnt[k] != cnt[k - 1] ? 1u : 0u;
+    forced[k] = f;
+    if (f) atomicAdd(&s_sum, 1u);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && s_sum)
+    atomicAdd((unsigned long long*)&counts[6], (unsigned long long)s_sum);
 }
 
 __global__ __launch_bounds__(256) void merge_emit_kernel(
@@ -288,11 +409,10 @@ void put_runs(const MergeRun* runs, uint32_t nruns, uint32_t n, const MergeScrat
   } while (base < nruns);
 }
 
-}  // namespace
-
-hipError_t launch_merge_plan(const MergeRun* runs, uint32_t nruns, uint32_t n,
-                             const MergeRule& rule, const MergeScratch& w, uint64_t* counts,
-                             hipStream_t s) {
+// The plan; v, x: the levels below the output and the stops' scratch, or null.
+hipError_t plan(const MergeRun* runs, uint32_t nruns, uint32_t n, const MergeRule& rule,
+                const MergeScratch& w, const VersionDev* v, const VersionScratch* x,
+                uint64_t* counts, hipStream_t s) {
   hipError_t e = hipMemsetAsync(counts, 0, 8 * kMergeCounts, s);
   if (e != hipSuccess) return e;
   if ((e = hipMemsetAsync(w.tot, 0, 32, s)) != hipSuccess) return e;
@@ -308,16 +428,57 @@ hipError_t launch_merge_plan(const MergeRun* runs, uint32_t nruns, uint32_t n,
     hipLaunchKernelGGL(merge_pass_kernel, dim3(grid256(n)), dim3(256), 0, s, w.table, w.first,
                        w.erun, nruns, n, rule.internal, width, w.kw[at], w.idx[at], w.kw[at ^ 1],
                        w.idx[at ^ 1]);
-  hipLaunchKernelGGL(neighbour_kernel, dim3(grid256(n)), dim3(256), 0, s, w.table, w.first, w.erun,
-                     n, rule, w.kw[at], w.idx[at], w.keep, w.klen, w.vlen, w.ksrc, w.vsrc, w.from,
-                     counts);
+  if (v)
+    hipLaunchKernelGGL(neighbour_kernel<true>, dim3(grid256(n)), dim3(256), 0, s, w.table, w.first,
+                       w.erun, n, rule, *v, w.kw[at], w.idx[at], w.keep, w.klen, w.vlen, w.ksrc,
+                       w.vsrc, w.from, counts);
+  else
+    hipLaunchKernelGGL(neighbour_kernel<false>, dim3(grid256(n)), dim3(256), 0, s, w.table, w.first,
+                       w.erun, n, rule, VersionDev{}, w.kw[at], w.idx[at], w.keep, w.klen, w.vlen,
+                       w.ksrc, w.vsrc, w.from, counts);
   if ((e = launch_scan(2, nullptr, w.keep, w.part, 0, w.pos, w.tot, n, s)) != hipSuccess) return e;
   if ((e = launch_scan(2, nullptr, w.klen, w.part, 0, w.koff, w.tot + 1, n, s)) != hipSuccess)
     return e;
   if ((e = launch_scan(2, nullptr, w.vlen, w.part, 0, w.voff, w.tot + 2, n, s)) != hipSuccess)
     return e;
   hipLaunchKernelGGL(plan_finish_kernel, dim3(1), dim3(1), 0, s, w.tot, n, counts);
+  if (!v) return hipGetLastError();
+  const dim3 g(grid256(n)), t(256);
+  if (v->first[1] == 0)      // nothing in level + 2: overlapped_bytes stays 0
+    return hipMemsetAsync(x->forced, 0, 4 * (size_t)n, s);
+  hipLaunchKernelGGL(passed_kernel, g, t, 0, s, w.table, w.first, w.erun, n, *v, w.idx[at], x->pg,
+                     x->mark);
+  hipLaunchKernelGGL(stop_next_kernel, g, t, 0, s, x->pg, v->limit, x->next, n);
+  // ceil(log2(n)) rounds reach the n-th stop of a chain of single positions.
+  const uint32_t* jin = x->next;
+  uint32_t* jout = x->ja;
+  for (uint64_t reach = 1; reach < n; reach <<= 1) {
+    hipLaunchKernelGGL(stop_jump_kernel, g, t, 0, s, x->mark, jin, jout, n);
+    jin = jout;
+    jout = jout == x->ja ? x->jb : x->ja;
+  }
+  // Position 0 is the chain's root, not a stop.
+  if ((e = hipMemsetAsync(x->mark, 0, 4, s)) != hipSuccess) return e;
+  if ((e = launch_scan(2, nullptr, x->mark, x->part, 0, x->sid, x->sid + n, n, s)) != hipSuccess)
+    return e;
+  hipLaunchKernelGGL(stop_fold_kernel, g, t, 0, s, n, w.keep, w.pos, x->mark, x->sid, x->cnt);
+  hipLaunchKernelGGL(forced_kernel, g, t, 0, s, w.tot, x->cnt, x->forced, counts);
   return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_merge_plan(const MergeRun* runs, uint32_t nruns, uint32_t n,
+                             const MergeRule& rule, const MergeScratch& w, uint64_t* counts,
+                             hipStream_t s) {
+  return plan(runs, nruns, n, rule, w, nullptr, nullptr, counts, s);
+}
+
+hipError_t launch_merge_plan_version(const MergeRun* runs, uint32_t nruns, uint32_t n,
+                                     const MergeRule& rule, const MergeScratch& w,
+                                     const VersionDev& v, const VersionScratch& x,
+                                     uint64_t* counts, hipStream_t s) {
+  return plan(runs, nruns, n, rule, w, &v, &x, counts, s);
 }
 
 hipError_t launch_merge_emit(uint32_t n, uint32_t n_out, const MergeScratch& w, uint8_t* keys,

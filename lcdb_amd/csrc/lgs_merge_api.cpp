@@ -46,6 +46,37 @@ struct MergeLayout {
   }
 };
 
+// The version plan's scratch: the merge's, the stops' arrays (their places
+// depend on n alone: lgs_merge_stops_dev finds `forced` without the levels),
+// then the levels as one upload [files, up_end).
+struct VersionLayout {
+  MergeLayout M;
+  size_t pg, next, ja, jb, mark, sid, cnt, forced, part, files, P, keys, up_end, total;
+  VersionLayout(size_t n, uint64_t nfiles, uint64_t key_bytes) : M(n) {
+    Layout L;
+    L.at = M.total;
+    pg = L.take(8 * n);
+    next = L.take(4 * n);
+    ja = L.take(4 * n);
+    jb = L.take(4 * n);
+    mark = L.take(4 * n + 4);
+    sid = L.take(8 * (n + 1));
+    cnt = L.take(4 * n);
+    forced = L.take(4 * n);
+    part = L.take(8 * scan_parts((uint32_t)n));
+    files = L.take(sizeof(VersionFile) * (size_t)nfiles);
+    P = L.take(8 * ((size_t)nfiles + 1));
+    keys = L.take((size_t)key_bytes + 16);
+    up_end = L.at;
+    total = L.at;
+  }
+  VersionScratch at(uint8_t* p) const {
+    return VersionScratch{(uint64_t*)(p + pg), (uint32_t*)(p + next), (uint32_t*)(p + ja),
+                          (uint32_t*)(p + jb), (uint32_t*)(p + mark), (uint64_t*)(p + sid),
+                          (uint32_t*)(p + cnt), (uint32_t*)(p + forced), (uint64_t*)(p + part)};
+  }
+};
+
 // The caller's runs as the kernels take them, and their total.
 int runs_in(const lgs_run* runs, uint32_t nruns, MergeRun* out, uint32_t* n_total) {
   if (nruns > LGS_MERGE_MAX_RUNS)
@@ -96,6 +127,97 @@ int lgs_merge_plan_dev(const lgs_run* runs, uint32_t nruns, int internal_keys, i
     return fail(LGS_EINVAL, "scratch %zu < %zu (lgs_merge_scratch)", scratch_bytes, M.total);
   LGS_HIP(launch_merge_plan(in, nruns, n, rule, M.at((uint8_t*)d_scratch), d_counts,
                             (hipStream_t)stream));
+  return LGS_OK;
+}
+
+size_t lgs_merge_version_scratch(uint32_t n_total, uint32_t nruns, uint64_t level_files,
+                                 uint64_t level_key_bytes) {
+  if (n_total > kMaxEntries || nruns > LGS_MERGE_MAX_RUNS || level_files > kMaxEntries ||
+      level_key_bytes > (1ull << 40))
+    return 0;
+  return VersionLayout(n_total, level_files, level_key_bytes).total;
+}
+
+int lgs_merge_plan_version_dev(const lgs_run* runs, uint32_t nruns, uint64_t smallest_snapshot,
+                               const lgs_level* levels, uint32_t nlevels,
+                               uint64_t max_grandparent_overlap, uint64_t* d_counts,
+                               void* d_scratch, size_t scratch_bytes, void* stream) {
+  MergeRun in[kMergeMaxRuns];
+  uint32_t n = 0;
+  LGS_TRY(runs_in(runs, nruns, in, &n));
+  if (nlevels > LGS_VERSION_MAX_LEVELS)
+    return fail(LGS_EINVAL, "%u levels: at most %d", nlevels, LGS_VERSION_MAX_LEVELS);
+  if (!d_counts || !d_scratch || (nlevels && !levels)) return fail(LGS_EINVAL, "NULL argument");
+  uint64_t nfiles = 0, key_bytes = 0;
+  for (uint32_t v = 0; v < nlevels; ++v) {
+    if (levels[v].n > kMaxEntries) return fail(LGS_EINVAL, "level %u: over 2^31 - 1 files", v);
+    if (levels[v].n && !levels[v].files) return fail(LGS_EINVAL, "NULL argument in level %u", v);
+    for (uint32_t f = 0; f < levels[v].n; ++f) {
+      const lgs_level_file& m = levels[v].files[f];
+      if (!m.smallest || !m.largest) return fail(LGS_EINVAL, "NULL key in level %u", v);
+      if (m.smallest_len < 8 || m.largest_len < 8)
+        return fail(LGS_EINVAL, "level %u, file %u: an internal key under 8 bytes", v, f);
+      key_bytes += (uint64_t)m.smallest_len + m.largest_len;
+    }
+    nfiles += levels[v].n;
+  }
+  if (nfiles > kMaxEntries || key_bytes > (1ull << 40))
+    return fail(LGS_EINVAL, "%llu files in the levels", (unsigned long long)nfiles);
+  const VersionLayout V(n, nfiles, key_bytes);
+  if (scratch_bytes < V.total)
+    return fail(LGS_EINVAL, "scratch %zu < %zu (lgs_merge_version_scratch)", scratch_bytes, V.total);
+  // The levels in one upload: the files, level + 2's prefix sums, the keys.
+  const uint32_t n0 = nlevels ? levels[0].n : 0;
+  std::vector<uint8_t> up(V.up_end - V.files);
+  VersionFile* files = (VersionFile*)up.data();
+  uint64_t* P = (uint64_t*)(up.data() + (V.P - V.files));
+  uint8_t* keys = up.data() + (V.keys - V.files);
+  uint8_t* d = (uint8_t*)d_scratch;
+  VersionDev dev{d + V.keys, (const VersionFile*)(d + V.files), (const uint64_t*)(d + V.P),
+                 {0, 0, 0, 0, 0, 0}, nlevels, max_grandparent_overlap};
+  uint64_t at = 0, f_at = 0;
+  for (uint32_t v = 0; v < nlevels; ++v) {
+    dev.first[v] = (uint32_t)f_at;
+    for (uint32_t f = 0; f < levels[v].n; ++f, ++f_at) {
+      const lgs_level_file& m = levels[v].files[f];
+      files[f_at] = VersionFile{at, at + m.smallest_len, m.smallest_len, m.largest_len};
+      memcpy(keys + at, m.smallest, m.smallest_len);
+      memcpy(keys + at + m.smallest_len, m.largest, m.largest_len);
+      at += (uint64_t)m.smallest_len + m.largest_len;
+    }
+  }
+  for (uint32_t v = nlevels; v <= kVersionMaxLevels; ++v) dev.first[v] = (uint32_t)f_at;
+  P[0] = 0;
+  for (uint32_t f = 0; f < n0; ++f) {
+    if (levels[0].files[f].file_size >= (1ull << 63) - P[f])
+      return fail(LGS_EINVAL, "the files of level + 2 hold 2^63 bytes or more");
+    P[f + 1] = P[f] + levels[0].files[f].file_size;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  // The upload reads `up`, so the stream is drained on every way out.
+  const int rc = [&]() -> int {
+    LGS_HIP(hipMemcpyAsync(d + V.files, up.data(), up.size(), hipMemcpyHostToDevice, s));
+    const MergeRule rule{1, 1, 0, smallest_snapshot};
+    LGS_HIP(launch_merge_plan_version(in, nruns, n, rule, V.M.at(d), dev, V.at(d), d_counts, s));
+    return LGS_OK;
+  }();
+  const hipError_t drained = hipStreamSynchronize(s);
+  LGS_TRY(rc);
+  LGS_HIP(drained);
+  return LGS_OK;
+}
+
+int lgs_merge_stops_dev(uint32_t n_total, uint32_t n_out, uint32_t* d_forced,
+                        const void* d_scratch, size_t scratch_bytes, void* stream) {
+  if (n_total > kMaxEntries || n_out > n_total)
+    return fail(LGS_EINVAL, "%u entries out of %u", n_out, n_total);
+  if (!d_scratch || (n_out && !d_forced)) return fail(LGS_EINVAL, "NULL argument");
+  const VersionLayout V(n_total, 0, 0);
+  if (scratch_bytes < V.total)
+    return fail(LGS_EINVAL, "scratch %zu < %zu (lgs_merge_version_scratch)", scratch_bytes, V.total);
+  if (n_out)
+    LGS_HIP(hipMemcpyAsync(d_forced, (const uint8_t*)d_scratch + V.forced, 4 * (size_t)n_out,
+                           hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return LGS_OK;
 }
 

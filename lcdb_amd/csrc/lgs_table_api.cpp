@@ -693,7 +693,7 @@ const char kFilterName[] = "filter.leveldb.BuiltinBloomFilter2";   // "filter." 
 
 // The builder's device scratch (BlockScratch, lgs_launch.h).
 struct BlockBuildScratch {
-  size_t lcp, sh, S, ca, cb, next, ja, jb, mark, bid, icut, ilen, part, total;
+  size_t lcp, sh, S, ca, cb, next, ja, jb, mark, bid, icut, ilen, part, fs, total;
   explicit BlockBuildScratch(uint32_t n) {
     const size_t m = (size_t)n + 1;
     Layout L;
@@ -710,6 +710,7 @@ struct BlockBuildScratch {
     icut = L.take(4 * m);
     ilen = L.take(4 * m);
     part = L.take(8 * scan_parts(n) + 8);
+    fs = L.take(8 * m);
     total = L.at;
   }
   BlockScratch at(uint8_t* p) const {
@@ -717,7 +718,7 @@ struct BlockBuildScratch {
                         (uint64_t*)(p + ca), (uint64_t*)(p + cb), (uint32_t*)(p + next),
                         (uint32_t*)(p + ja), (uint32_t*)(p + jb), (uint32_t*)(p + mark),
                         (uint64_t*)(p + bid), (uint32_t*)(p + icut), (uint32_t*)(p + ilen),
-                        (uint64_t*)(p + part)};
+                        (uint64_t*)(p + part), (uint64_t*)(p + fs)};
   }
 };
 
@@ -833,6 +834,19 @@ int lgs_block_cut_dev(const uint8_t* d_keys, const uint64_t* d_key_off, const ui
                       uint32_t restart_interval, int internal_keys, uint32_t* d_block_first,
                       uint64_t* d_raw_off, uint32_t* d_raw_len, uint64_t* d_ikey_off,
                       uint64_t* d_counts, void* d_scratch, size_t scratch_bytes, void* stream) {
+  return lgs_block_cut_forced_dev(d_keys, d_key_off, d_key_len, d_val_len, n, block_size,
+                                  restart_interval, internal_keys, nullptr, d_block_first,
+                                  d_raw_off, d_raw_len, d_ikey_off, d_counts, d_scratch,
+                                  scratch_bytes, stream);
+}
+
+int lgs_block_cut_forced_dev(const uint8_t* d_keys, const uint64_t* d_key_off,
+                             const uint32_t* d_key_len, const uint32_t* d_val_len, uint32_t n,
+                             uint64_t block_size, uint32_t restart_interval, int internal_keys,
+                             const uint32_t* d_forced, uint32_t* d_block_first,
+                             uint64_t* d_raw_off, uint32_t* d_raw_len, uint64_t* d_ikey_off,
+                             uint64_t* d_counts, void* d_scratch, size_t scratch_bytes,
+                             void* stream) {
   LGS_TRY(block_args(n, restart_interval, internal_keys));
   if (!d_block_first || !d_raw_off || !d_raw_len || !d_ikey_off || !d_counts || !d_scratch ||
       (n && (!d_keys || !d_key_off || !d_key_len || !d_val_len)))
@@ -842,7 +856,7 @@ int lgs_block_cut_dev(const uint8_t* d_keys, const uint64_t* d_key_off, const ui
     return fail(LGS_EINVAL, "scratch %zu < %zu (lgs_block_build_scratch)", scratch_bytes, B.total);
   const BlockIn in{d_keys, d_key_off, d_key_len, nullptr, nullptr, d_val_len, n};
   const BlockCut out{d_block_first, d_raw_off, d_raw_len, d_ikey_off, d_counts};
-  LGS_HIP(launch_block_cut(in, block_size, restart_interval, internal_keys ? 8u : 0u,
+  LGS_HIP(launch_block_cut(in, block_size, restart_interval, internal_keys ? 8u : 0u, d_forced,
                            B.at((uint8_t*)d_scratch), out, (hipStream_t)stream));
   return LGS_OK;
 }
@@ -909,7 +923,8 @@ int lgs_block_build_host(const uint8_t* keys, const uint64_t* key_off, const uin
   const BlockIn in = entries_in(d, E, n);
   const BlockCut cut = K.at(d, (uint64_t*)(d + o_cnt));
   const uint32_t trim = internal_keys ? 8u : 0u;
-  LGS_HIP(launch_block_cut(in, block_size, restart_interval, trim, B.at(d + o_scr), cut, c.stream));
+  LGS_HIP(launch_block_cut(in, block_size, restart_interval, trim, nullptr, B.at(d + o_scr), cut,
+                           c.stream));
   LGS_HIP(hipMemcpyAsync(h + o_cnt, d + o_cnt, 8 * kBlockCounts, hipMemcpyDeviceToHost, c.stream));
   LGS_HIP(hipStreamSynchronize(c.stream));
   const uint64_t* cnt = (const uint64_t*)(h + o_cnt);
@@ -968,7 +983,8 @@ struct BuildLayout {
          o_tpoff = 0, o_tptotal = 0, o_tfoff = 0, o_tpart = 0;
   // The file plan (lgs_tables_build_dev only).
   size_t p_next = 0, p_ja = 0, p_jb = 0, p_mark = 0, p_fid = 0, p_fof = 0, p_fstart = 0,
-         p_rel = 0, p_flen = 0, p_fblock = 0, p_fentry = 0, p_fbegin = 0, p_fikey = 0, p_dst = 0;
+         p_rel = 0, p_flen = 0, p_fblock = 0, p_fentry = 0, p_fbegin = 0, p_fikey = 0, p_dst = 0,
+         p_fflag = 0, p_ffs = 0;
 
   // image: the framed stream is followed by one table's tail (the host call);
   // plan: room for the file plan.
@@ -1048,6 +1064,8 @@ struct BuildLayout {
       p_fbegin = L.take(8 * m);
       p_fikey = L.take(8 * m);
       p_dst = L.take(8 * m);
+      p_fflag = L.take(4 * m);
+      p_ffs = L.take(8 * m);
     }
     return LGS_OK;
   }
@@ -1055,6 +1073,7 @@ struct BuildLayout {
     return FilePlan{(uint32_t*)(p + p_next), (uint32_t*)(p + p_ja), (uint32_t*)(p + p_jb),
                     (uint32_t*)(p + p_mark), (uint64_t*)(p + p_fid), (uint32_t*)(p + p_fof),
                     (uint64_t*)(p + p_fstart), (uint64_t*)(p + p_rel), (uint32_t*)(p + p_flen),
+                    (uint32_t*)(p + p_fflag), (uint64_t*)(p + p_ffs),
                     (uint32_t*)(p + p_fblock), (uint32_t*)(p + p_fentry),
                     (uint64_t*)(p + p_fbegin), (uint64_t*)(p + p_fikey),
                     (uint64_t*)(p + o_nfiles)};
@@ -1072,11 +1091,12 @@ struct DataBlocks {
 // file: the cut's keys stand).  One synchronisation, for the block count.
 static int build_data(const BuildLayout& A, uint8_t* h, uint8_t* d, hipStream_t s,
                       const BlockIn& in, uint64_t key_bytes, uint64_t block_size,
-                      uint32_t restart_interval, uint32_t trim, int compression, bool ikeys,
-                      DataBlocks* out) {
+                      uint32_t restart_interval, uint32_t trim, const uint32_t* forced,
+                      int compression, bool ikeys, DataBlocks* out) {
   const BlockBuildScratch B(A.n);
   const BlockCut cut = A.K.at(d, (uint64_t*)(d + A.o_cnt));
-  LGS_HIP(launch_block_cut(in, block_size, restart_interval, trim, B.at(d + A.o_scr), cut, s));
+  LGS_HIP(launch_block_cut(in, block_size, restart_interval, trim, forced, B.at(d + A.o_scr), cut,
+                           s));
   LGS_HIP(hipMemcpyAsync(h + A.o_cnt, d + A.o_cnt, 8 * kBlockCounts, hipMemcpyDeviceToHost, s));
   LGS_HIP(hipStreamSynchronize(s));
   const uint64_t* cnt = (const uint64_t*)(h + A.o_cnt);
@@ -1144,7 +1164,7 @@ static int build_tail(const BuildLayout& A, uint8_t* h, uint8_t* d, hipStream_t 
   if (f.nb) {
     // The index block's entries (:229-239, :332-341): index key -> handle, one
     // block whatever its size, restart interval 1 (:87).
-    LGS_HIP(launch_block_cut(iin, ~0ull, 1, 0, B.at(d + A.o_scr), cut2, s));
+    LGS_HIP(launch_block_cut(iin, ~0ull, 1, 0, nullptr, B.at(d + A.o_scr), cut2, s));
     LGS_HIP(hipMemcpyAsync(h + A.o_cnt2, d + A.o_cnt2, 8 * kBlockCounts, hipMemcpyDeviceToHost, s));
     if (!f.len_known)
       LGS_HIP(hipMemcpyAsync(h + A.o_end, d + A.o_end, 8, hipMemcpyDeviceToHost, s));
@@ -1308,7 +1328,7 @@ int lgs_table_build_host(const uint8_t* keys, const uint64_t* key_off, const uin
     entries_stage(h, E, keys, key_off, key_len, vals, val_off, val_len, n);
     LGS_HIP(hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, s));
     LGS_TRY(build_data(A, h, d, s, in, E.kb, block_size, restart_interval, internal_keys ? 8u : 0u,
-                       compression, true, &D));
+                       nullptr, compression, true, &D));
     LGS_HIP(launch_handle_values((const uint64_t*)(d + A.o_hoff), (const uint64_t*)(d + A.o_hsize),
                                  nullptr, (const uint64_t*)(d + A.K.ioff), (uint32_t)D.nb,
                                  d + A.o_hval, (uint64_t*)(d + A.o_ivoff),
@@ -1340,11 +1360,19 @@ int lgs_table_build_host(const uint8_t* keys, const uint64_t* key_off, const uin
 
 size_t lgs_tables_build_bound(uint32_t n, uint64_t key_bytes, uint64_t value_bytes,
                               int bits_per_key, uint64_t max_file_size, uint32_t* max_files) {
-  // Every file but the last holds at least max_file_size bytes of data blocks,
-  // and every file at least one entry; per file the tail's constant parts, the
-  // spare bytes and the alignment of file_slot (under 320 bytes).
+  return lgs_tables_build_forced_bound(n, key_bytes, value_bytes, bits_per_key, max_file_size, 0,
+                                       max_files);
+}
+
+size_t lgs_tables_build_forced_bound(uint32_t n, uint64_t key_bytes, uint64_t value_bytes,
+                                     int bits_per_key, uint64_t max_file_size, uint32_t n_forced,
+                                     uint32_t* max_files) {
+  // Every file but the last holds at least max_file_size bytes of data blocks
+  // or ends before a forced start, and every file at least one entry; per
+  // file the tail's constant parts, the spare bytes and the alignment of
+  // file_slot (under 320 bytes).
   const uint64_t data = key_bytes + value_bytes + 19ull * n + (uint64_t)LGS_TRAILER_SIZE * n;
-  uint64_t files = max_file_size ? data / max_file_size + 1 : n;
+  uint64_t files = (max_file_size ? data / max_file_size + 1 : n) + n_forced;
   if (files > n) files = n;
   if (max_files) *max_files = (uint32_t)files;
   return (size_t)(lgs_table_build_bound(n, key_bytes, value_bytes, bits_per_key) + 320 * files);
@@ -1358,6 +1386,23 @@ int lgs_tables_build_dev(const uint8_t* d_keys, const uint64_t* d_key_off, const
                          size_t files_cap, uint64_t* d_file_off, uint64_t* d_file_size,
                          uint32_t* d_file_first, uint32_t files_cap_count, uint32_t* n_files,
                          uint64_t* files_bytes, void* stream) {
+  return lgs_tables_build_forced_dev(d_keys, d_key_off, d_key_len, d_vals, d_val_off, d_val_len, n,
+                                     key_bytes, value_bytes, block_size, restart_interval,
+                                     compression, bits_per_key, internal_keys, max_file_size,
+                                     nullptr, d_files, files_cap, d_file_off, d_file_size,
+                                     d_file_first, files_cap_count, n_files, files_bytes, stream);
+}
+
+int lgs_tables_build_forced_dev(const uint8_t* d_keys, const uint64_t* d_key_off,
+                                const uint32_t* d_key_len, const uint8_t* d_vals,
+                                const uint64_t* d_val_off, const uint32_t* d_val_len, uint32_t n,
+                                uint64_t key_bytes, uint64_t value_bytes, uint64_t block_size,
+                                uint32_t restart_interval, int compression, int bits_per_key,
+                                int internal_keys, uint64_t max_file_size,
+                                const uint32_t* d_forced, uint8_t* d_files, size_t files_cap,
+                                uint64_t* d_file_off, uint64_t* d_file_size,
+                                uint32_t* d_file_first, uint32_t files_cap_count,
+                                uint32_t* n_files, uint64_t* files_bytes, void* stream) {
   LGS_TRY(build_args(n, restart_interval, compression, bits_per_key, internal_keys));
   if (!n_files || !files_bytes) return fail(LGS_EINVAL, "NULL argument");
   *n_files = 0;
@@ -1383,8 +1428,8 @@ int lgs_tables_build_dev(const uint8_t* d_keys, const uint64_t* d_key_off, const
   const uint32_t trim = internal_keys ? 8u : 0u;
   const BlockIn in{d_keys, d_key_off, d_key_len, d_vals, d_val_off, d_val_len, n};
   DataBlocks D;
-  LGS_TRY(build_data(A, h, d, s, in, key_bytes, block_size, restart_interval, trim, compression,
-                     false, &D));
+  LGS_TRY(build_data(A, h, d, s, in, key_bytes, block_size, restart_interval, trim, d_forced,
+                     compression, false, &D));
   const uint32_t nb = (uint32_t)D.nb;
   // The files (second synchronisation: their number; third: one row each).
   const BlockBuildScratch B(n);
@@ -1392,8 +1437,8 @@ int lgs_tables_build_dev(const uint8_t* d_keys, const uint64_t* d_key_off, const
   const FilePlan P = A.plan_at(d);
   const uint64_t* d_hoff = (const uint64_t*)(d + A.o_hoff);
   const uint64_t* d_hsize = (const uint64_t*)(d + A.o_hsize);
-  LGS_HIP(launch_file_plan(in, trim, nb, d_hoff, d_hsize, max_file_size, B.at(d + A.o_scr), cut,
-                           P, s));
+  LGS_HIP(launch_file_plan(in, trim, nb, d_hoff, d_hsize, max_file_size, d_forced,
+                           B.at(d + A.o_scr), cut, P, s));
   LGS_HIP(hipMemcpyAsync(h + A.o_nfiles, d + A.o_nfiles, 8, hipMemcpyDeviceToHost, s));
   LGS_HIP(hipStreamSynchronize(s));
   const uint64_t nf = *(const uint64_t*)(h + A.o_nfiles);

@@ -57,7 +57,7 @@ _L = _native.lib()
 
 __all__ = [
     "crc32c_batch", "write_blocks", "read_blocks", "write_blocks_host", "read_blocks_host",
-    "index_host", "FILTER_NAME", "seek_blocks_host", "block_entries", "block_entries_host", "ScanError", "merge_runs", "merge_runs_host", "compact_tables", "compact_to_files", "build_tables_dev", "MergeError", "get_host", "open_table", "OpenTable", "build_blocks", "build_blocks_host", "build_table_host",
+    "index_host", "FILTER_NAME", "seek_blocks_host", "block_entries", "block_entries_host", "ScanError", "merge_runs", "merge_runs_host", "merge_runs_version", "compact_tables", "compact_to_files", "compact_in_version", "build_tables_dev", "MergeError", "get_host", "open_table", "OpenTable", "build_blocks", "build_blocks_host", "build_table_host",
     "LGS_NO_COMPRESSION", "LGS_SNAPPY_COMPRESSION", "LGS_TRAILER_SIZE", "LGS_ST_OK",
     "LGS_ST_CORRUPT", "LGS_ST_NOSPACE", "LGS_ST_IOERR", "LGS_ST_BADCRC", "LGS_ST_BADTYPE",
     "LGS_GET_NOTFOUND", "LGS_GET_FOUND", "LGS_GET_DELETED", "LGS_GET_CORRUPT",
@@ -901,6 +901,89 @@ def merge_runs(runs, internal_keys: bool = False, drop: bool = False, smallest_s
             "val_bytes": vb, "max_key": mk}
 
 
+def _pack_levels(levels):
+    """levels ([[(smallest, largest, file_size)]]) as an lgs_level array; the
+    second value keeps the memory it points into alive."""
+    import ctypes as C
+    arr = (_native.LgsLevel * max(len(levels), 1))()
+    keep, nfiles, key_bytes = [], 0, 0
+    for v, files in enumerate(levels):
+        fa = (_native.LgsLevelFile * max(len(files), 1))()
+        for f, (lo, hi, size) in enumerate(files):
+            lo, hi = bytes(lo), bytes(hi)
+            bl, bh = C.create_string_buffer(lo, len(lo) + 1), C.create_string_buffer(hi, len(hi) + 1)
+            keep += [bl, bh]
+            fa[f] = _native.LgsLevelFile(C.addressof(bl), len(lo), C.addressof(bh), len(hi), int(size))
+            key_bytes += len(lo) + len(hi)
+        keep.append(fa)
+        arr[v] = _native.LgsLevel(fa, len(files))
+        nfiles += len(files)
+    return arr, keep, nfiles, key_bytes
+
+
+def merge_runs_version(runs, smallest_snapshot: int, levels, max_grandparent_overlap_bytes: int,
+                       stream=None):
+    """``merge_runs`` with internal keys and the drop rule for a compaction
+    inside a version (lgs_merge_plan_version_dev + lgs_merge_emit_dev +
+    lgs_merge_stops_dev).
+
+    ``levels``: the files of the levels below the output, level + 2 first, at
+    most 5 lists of ``(smallest_ikey, largest_ikey, file_size)`` in each
+    level's order.  A deletion at or under ``smallest_snapshot`` is dropped
+    where ldb_compaction_is_base_level_for_key holds for its user key, and
+    ldb_compaction_should_stop_before runs against ``levels[0]`` with the
+    limit ``max_grandparent_overlap_bytes``.  Returns ``merge_runs``' dict
+    plus ``forced`` (int32 per kept entry: 1 where a stop closed the open
+    output file just before it) and the int ``n_forced``."""
+    torch = _torch()
+    k = len(runs)
+    arr = (_native.LgsRun * max(k, 1))()
+    n_total = 0
+    dev = None
+    for r, run in enumerate(runs):
+        n = int(run["n"]) if "n" in run else int(run["key_len"].numel())
+        dev = run["keys"].device if dev is None else dev
+        arr[r] = _native.LgsRun(*(run[f].data_ptr() for f in
+                                  ("keys", "key_off", "key_len", "vals", "val_off", "val_len")), n)
+        n_total += n
+    dev = torch.device("cuda") if dev is None else dev
+    sp = _stream_ptr(stream)
+    lv, alive, nfiles, key_bytes = _pack_levels(levels)
+    scr = torch.empty(max(int(_L.lgs_merge_version_scratch(
+        min(n_total, 0x7fffffff), min(k, _native.LGS_MERGE_MAX_RUNS), nfiles, key_bytes)), 1),
+        dtype=torch.uint8, device=dev)
+    counts = torch.empty(8, dtype=torch.int64, device=dev)
+    check(_L.lgs_merge_plan_version_dev(arr, k, int(smallest_snapshot), lv, len(levels),
+                                        int(max_grandparent_overlap_bytes), counts.data_ptr(),
+                                        scr.data_ptr(), int(scr.numel()), sp),
+          "lgs_merge_plan_version_dev")
+    del alive
+    cnt = [int(x) & _NO_RUN for x in counts.cpu()]
+    if cnt[5] != _NO_RUN:
+        e = MergeError(f"lgs_merge_plan_version_dev: run {cnt[5]} is not sorted or has a short key")
+        e.rc, e.run = _native.LGS_EINVAL, cnt[5]
+        raise e
+    n, kb, vb, mk, dropped = cnt[:5]
+    keys = torch.empty(kb + 16, dtype=torch.uint8, device=dev)
+    vals = torch.empty(vb + 16, dtype=torch.uint8, device=dev)
+    key_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    val_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    i32 = lambda: torch.empty(max(n, 1), dtype=torch.int32, device=dev)   # noqa: E731
+    key_len, val_len, src_run, src_index, forced = i32(), i32(), i32(), i32(), i32()
+    check(_L.lgs_merge_emit_dev(arr, k, n, keys.data_ptr(), key_off.data_ptr(),
+                                key_len.data_ptr(), vals.data_ptr(), val_off.data_ptr(),
+                                val_len.data_ptr(), src_run.data_ptr(), src_index.data_ptr(),
+                                scr.data_ptr(), int(scr.numel()), sp), "lgs_merge_emit_dev")
+    check(_L.lgs_merge_stops_dev(n_total, n, forced.data_ptr(), scr.data_ptr(), int(scr.numel()),
+                                 sp), "lgs_merge_stops_dev")
+    if stream is not None:
+        scr.record_stream(stream)
+    return {"keys": keys, "key_off": key_off, "key_len": key_len[:n], "vals": vals,
+            "val_off": val_off, "val_len": val_len[:n], "src_run": src_run[:n],
+            "src_index": src_index[:n], "n": n, "dropped": dropped, "key_bytes": kb,
+            "val_bytes": vb, "max_key": mk, "forced": forced[:n], "n_forced": cnt[6]}
+
+
 def merge_runs_host(runs, internal_keys: bool = False, drop: bool = False,
                     smallest_snapshot: int = 0, drop_deletions: bool = False, caps=None):
     """lgs_merge_host on lists of (key, value): returns ([(key, value)],
@@ -949,7 +1032,8 @@ _NO_SPLIT = (1 << 64) - 1
 
 def build_tables_dev(run, block_size: int = 4096, restart_interval: int = 16,
                      compression: int = LGS_SNAPPY_COMPRESSION, bits_per_key: int = 0,
-                     internal_keys: bool = False, max_file_size: int = _NO_SPLIT, stream=None):
+                     internal_keys: bool = False, max_file_size: int = _NO_SPLIT, stream=None,
+                     forced=None):
     """The .ldb files a compaction writes for sorted entries in device memory,
     left in device memory (lgs_tables_build_dev): lcdb closes an output file
     once ldb_tablegen_size reaches ``max_file_size`` (db_impl.c:1417-1425);
@@ -961,7 +1045,12 @@ def build_tables_dev(run, block_size: int = 4096, restart_interval: int = 16,
     the images), ``file_off`` / ``file_size`` (int64, n_files), ``file_first``
     (int32, n_files + 1: file f holds entries file_first[f]:file_first[f+1])
     and the int ``n_files``.  No entries give no file.  The stream is drained
-    when it returns."""
+    when it returns.
+
+    ``forced`` (int32 device tensor, one flag per entry, as
+    ``merge_runs_version`` returns it) makes every flagged entry behind the
+    first start a block and a file (lgs_tables_build_forced_dev): the files
+    ldb_compaction_should_stop_before closes early.  None: no such starts."""
     import ctypes as C
     torch = _torch()
     n = int(run["n"]) if "n" in run else int(run["key_len"].numel())
@@ -969,22 +1058,32 @@ def build_tables_dev(run, block_size: int = 4096, restart_interval: int = 16,
     kb = int(run["key_bytes"]) if "key_bytes" in run else int(run["key_len"].sum())
     vb = int(run["val_bytes"]) if "val_bytes" in run else int(run["val_len"].sum())
     max_files = C.c_uint32(0)
-    cap = int(_L.lgs_tables_build_bound(n, kb, vb, int(bits_per_key), int(max_file_size),
-                                        C.byref(max_files)))
+    if forced is None:
+        cap = int(_L.lgs_tables_build_bound(n, kb, vb, int(bits_per_key), int(max_file_size),
+                                            C.byref(max_files)))
+    else:
+        if int(forced.numel()) < n:
+            raise ValueError(f"{int(forced.numel())} forced flags for {n} entries")
+        n_forced = int(run["n_forced"]) if "n_forced" in run else int((forced[:n] != 0).sum())
+        cap = int(_L.lgs_tables_build_forced_bound(n, kb, vb, int(bits_per_key),
+                                                   int(max_file_size), n_forced,
+                                                   C.byref(max_files)))
     files = torch.empty(cap + 16, dtype=torch.uint8, device=dev)
     nf_cap = max(int(max_files.value), 1)
     file_off = torch.zeros(nf_cap, dtype=torch.int64, device=dev)
     file_size = torch.zeros(nf_cap, dtype=torch.int64, device=dev)
     file_first = torch.zeros(nf_cap + 1, dtype=torch.int32, device=dev)
     nf, used = C.c_uint32(0), C.c_uint64(0)
-    check(_L.lgs_tables_build_dev(*(run[f].data_ptr() for f in
-                                    ("keys", "key_off", "key_len", "vals", "val_off", "val_len")),
-                                  n, kb, vb, int(block_size), int(restart_interval),
-                                  int(compression), int(bits_per_key), 1 if internal_keys else 0,
-                                  int(max_file_size), files.data_ptr(), cap, file_off.data_ptr(),
-                                  file_size.data_ptr(), file_first.data_ptr(), nf_cap,
-                                  C.byref(nf), C.byref(used), _stream_ptr(stream)),
-          "lgs_tables_build_dev")
+    ptrs = [run[f].data_ptr() for f in ("keys", "key_off", "key_len", "vals", "val_off", "val_len")]
+    head = (n, kb, vb, int(block_size), int(restart_interval), int(compression),
+            int(bits_per_key), 1 if internal_keys else 0, int(max_file_size))
+    tail = (files.data_ptr(), cap, file_off.data_ptr(), file_size.data_ptr(),
+            file_first.data_ptr(), nf_cap, C.byref(nf), C.byref(used), _stream_ptr(stream))
+    if forced is None:
+        check(_L.lgs_tables_build_dev(*ptrs, *head, *tail), "lgs_tables_build_dev")
+    else:
+        check(_L.lgs_tables_build_forced_dev(*ptrs, *head, forced.data_ptr(), *tail),
+              "lgs_tables_build_forced_dev")
     if stream is not None:
         for t in (files, file_off, file_size, file_first):
             t.record_stream(stream)
@@ -1029,18 +1128,30 @@ def compact_to_files(tables, smallest_snapshot: int, drop_deletions: bool, block
 
     ``drop_deletions`` is ldb_compaction_is_base_level_for_key for every key
     of the call; ``max_output_file_size`` is the compaction's
-    (db_impl.c:1417-1425).  should_stop_before is not applied.
-    Returns one dict per file, in file order: ``image`` (bytes), ``smallest``
-    and ``largest`` (the internal keys of its first and last entry) and
-    ``entries``: what ldb_edit_add_file takes.  No kept entry, no file."""
+    (db_impl.c:1417-1425).  Neither depends on the levels below the output:
+    ``compact_in_version`` takes those and applies
+    ldb_compaction_should_stop_before and the per-key base level (DESIGN
+    §4.10).  Returns one dict per file, in file order: ``image`` (bytes),
+    ``smallest`` and ``largest`` (the internal keys of its first and last
+    entry) and ``entries``: what ldb_edit_add_file takes.  No kept entry, no
+    file."""
+    return _compact_files(tables, bits_per_key, verify, lambda runs: merge_runs(
+        runs, internal_keys=True, drop=True, smallest_snapshot=smallest_snapshot,
+        drop_deletions=drop_deletions), block_size, restart_interval, compression,
+        max_output_file_size)
+
+
+def _compact_files(tables, bits_per_key, verify, merge, block_size, restart_interval, compression,
+                   max_output_file_size):
+    """scan -> ``merge(runs)`` -> build, and the files' rows for the host."""
     torch = _torch()
     opened = []
     try:
         runs = _scan_runs(tables, bits_per_key, verify, opened)
-        m = merge_runs(runs, internal_keys=True, drop=True, smallest_snapshot=smallest_snapshot,
-                       drop_deletions=drop_deletions)
+        m = merge(runs)
         b = build_tables_dev(m, block_size, restart_interval, compression, bits_per_key,
-                             internal_keys=True, max_file_size=max_output_file_size)
+                             internal_keys=True, max_file_size=max_output_file_size,
+                             forced=m.get("forced"))
         nf = b["n_files"]
         if nf == 0:
             return []
@@ -1066,12 +1177,37 @@ def compact_to_files(tables, smallest_snapshot: int, drop_deletions: bool, block
     return out
 
 
+def compact_in_version(tables, smallest_snapshot: int, levels, block_size: int = 4096,
+                       restart_interval: int = 16, compression: int = LGS_SNAPPY_COMPRESSION,
+                       bits_per_key: int = 0, verify: bool = True,
+                       max_output_file_size: int = 2 << 20,
+                       max_grandparent_overlap_bytes: Optional[int] = None):
+    """``compact_to_files`` for a compaction at level L of a version whose
+    levels L + 2 .. 6 hold ``levels`` (a list of at most 5 lists of
+    ``(smallest_ikey, largest_ikey, file_size)``, level L + 2 first, each in
+    its level's order): lcdb's loop, db_impl.c:1352-1425, as lcdb runs it.
+
+    ldb_compaction_should_stop_before closes the output file before a key
+    once the file overlaps more than ``max_grandparent_overlap_bytes`` of
+    ``levels[0]`` (None: 10 x ``max_output_file_size``, version_set.c:57), and
+    a deletion is dropped where ldb_compaction_is_base_level_for_key holds
+    for its user key.  Level L + 2 is given whole: files before the inputs are
+    passed by the first key at no cost, files behind them are never reached,
+    so the result is that of lcdb's overlapping subset.  Returns what
+    ``compact_to_files`` returns."""
+    limit = (10 * max_output_file_size if max_grandparent_overlap_bytes is None
+             else max_grandparent_overlap_bytes)
+    return _compact_files(tables, bits_per_key, verify, lambda runs: merge_runs_version(
+        runs, smallest_snapshot, levels, limit), block_size, restart_interval, compression,
+        max_output_file_size)
+
+
 def compact_tables(tables, smallest_snapshot: int, drop_deletions: bool, block_size: int = 4096,
                    restart_interval: int = 16, compression: int = LGS_SNAPPY_COMPRESSION,
                    bits_per_key: int = 0, verify: bool = True) -> bytes:
     """One compaction's output as one table: ``compact_to_files`` with no
-    limit on the output file's size (should_stop_before and
-    max_output_file_size are not applied), so scan, merge and build all stay
+    limit on the output file's size (max_output_file_size is not applied, nor
+    ldb_compaction_should_stop_before: see ``compact_in_version``), so scan, merge and build all stay
     in device memory and only the image is downloaded.  A compaction that
     keeps no entry gives lcdb's empty table, as ``build_table_host`` does."""
     files = compact_to_files(tables, smallest_snapshot, drop_deletions, block_size,

@@ -24,8 +24,14 @@ dropped and max_output_file_size = 2 MiB.
   one-file image is what compact_tables returned (SHA-256, compared with the
   parent's when --parent-json is given).
 
+--version measures the compaction inside a version instead:
+compact_in_version on the same inputs against 64 level + 2 files of 1 MiB
+spread over the key space, with a limit that lets about ten stops fire, and
+compact_to_files beside it, both end to end as above; the result goes to
+profiles/compact_version.json.
+
 Writes one JSON object to --out (default profiles/compact.json) and prints it.
-usage: python tools/bench_compact.py [--entries N] [--tables K]
+usage: python tools/bench_compact.py [--entries N] [--tables K] [--version]
 """
 from __future__ import annotations
 
@@ -52,8 +58,15 @@ def main() -> None:
     p.add_argument("--parent-json", default=None)
     p.add_argument("--build-only", action="store_true",
                    help="the build alone (for a kernel trace): no inputs, no end-to-end runs")
-    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "compact.json"))
+    p.add_argument("--version", action="store_true",
+                   help="compact_in_version over --level-files level + 2 files, and "
+                        "compact_to_files on the same inputs (DESIGN §4.10)")
+    p.add_argument("--level-files", type=int, default=64)
+    p.add_argument("--out", default=None)
     a = p.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles",
+                             "compact_version.json" if a.version else "compact.json")
 
     import numpy as np
     import torch
@@ -98,6 +111,41 @@ def main() -> None:
             if i >= 1:
                 ts.append(time.perf_counter() - t0)
         return stats(ts), res
+
+    if a.version:
+        # The same inputs inside a version: level + 2 holds
+        # --level-files files of 1 MiB over the key space with gaps between
+        # them, and the limit lets about ten stops fire.  Nothing is dropped.
+        nl = a.level_files
+        span = n // nl
+        tag = lambda s: ((s << 8) | 1).to_bytes(8, "little")      # noqa: E731
+        lv = [(b"%016d" % (j * span + span // 8) + tag(5), b"%016d" % (j * span + span // 2) + tag(1),
+               1 << 20) for j in range(nl)]
+        limit = (nl << 20) // 10 - 1
+        tv, fv = wall(lambda: table.compact_in_version(
+            images, n + 1, [lv], max_output_file_size=a.max_file_size,
+            max_grandparent_overlap_bytes=limit), a.e2e_iters)
+        tp, fp = wall(lambda: table.compact_to_files(images, n + 1, False,
+                                                     max_output_file_size=a.max_file_size),
+                      a.e2e_iters)
+        ok = sum(f["entries"] for f in fv) == n == sum(f["entries"] for f in fp)
+        ok = ok and len(fv) > len(fp)
+        # The same entries in the same order, cut in other places.
+        out["workload"] += f"; level + 2: {nl} files of 1 MiB, limit {limit}"
+        out["compact_in_version"] = dict(tv, files=len(fv), level_files=nl, limit=limit,
+                                         output_bytes=sum(len(f["image"]) for f in fv))
+        out["compact_to_files"] = dict(tp, files=len(fp),
+                                       output_bytes=sum(len(f["image"]) for f in fp))
+        out["in_version_vs_to_files"] = tv["median_ms"] / tp["median_ms"]
+        out["ms_per_extra_file"] = (tv["median_ms"] - tp["median_ms"]) / (len(fv) - len(fp))
+        out["verified"] = bool(ok)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1, sort_keys=True)
+            f.write("\n")
+        print(json.dumps(out, indent=1, sort_keys=True))
+        if not ok:
+            sys.exit("bench_compact: result check failed")
+        return
 
     ok, one, files = True, None, None
     if not a.build_only:
