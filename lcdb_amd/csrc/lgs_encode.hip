@@ -488,6 +488,10 @@ struct PostLanes {
   uint32_t e0, e1, bm, vu, l4;
 };
 constexpr uint32_t kProbesPerBatch = kWave - 2;
+// The batch after a copy has every lane on while its last lane's next probe
+// is inside the limit (snappy.c:143): at + 1 + probe_off(62) <= n - kMargin,
+// at the copy's end.  kInterior is that distance from the chunk's end (125).
+constexpr uint32_t kInterior = kMargin + 1 + probe_off(kProbesPerBatch);
 __device__ __forceinline__ PostLanes post_lanes(uint32_t lane) {
   const uint32_t pk = lane >= 2 ? lane - 2 : 0;
   constexpr uint32_t s0 = 1u - kEndBias;              // the search's start, from am
@@ -547,6 +551,24 @@ constexpr uint32_t kPostLast = probe_off(kProbesPerBatch - 1);
 // round 4 took a v_mov and a v_cndmask per word), the order check is a
 // compare ORed into a scalar mask that encode_chunk looks at once per chunk,
 // and the match test is one compare whose VCC is the branch.
+//
+// Round 13: the batch after a copy pays nothing for the chunk's edges while
+// the copy ended kInterior bytes or more before the chunk's end, where every
+// lane of it is a probe (97 % of C2's rounds).  What a lane that is no probe
+// must not do is kept in three per-lane words that only the chunk's end
+// changes (post_batch): the table swap's mask (0xffff; 0 makes the swap a
+// read), the word that keeps a lane from matching (~pl.vu), and vmask.  A
+// scalar test on the copy's end takes the few batches near the chunk's end
+// through the code that recomputes them, a branch around it and nothing
+// else, so the loop keeps its one exit.  (Two forms of the batch chosen by
+// that test were built first: an if/else inside the loop, or a second exit,
+// costs selector moves and three more branches a round once the compiler has
+// given the loop one exit again, and measured slower than the parent.)
+// Lane B's bytes at+4..at+6 (snappy.c:182) are the low three bytes of lane
+// 5's probe word (lane 5 probes at + 4, and is inside the chunk whenever B
+// is a probe), moved with one DPP v_mov: the third probe dword, its read,
+// its wait in front of the swap and its v_alignbyte are gone from every
+// batch after a copy.
 //
 // One pass over a chunk: encode_chunk's parse, with the batch's table swap
 // done in one atomic (SERIAL = false, the product's path) or lane by lane
@@ -660,6 +682,44 @@ __device__ __forceinline__ uint32_t encode_pass(IN& x, uint32_t n, uint16_t* tab
     }
     return ballot(((xv ^ yv) | w) == 0);                          // snappy.c:152
   };
+  // ---- the batch after a copy, in the product's first pass over an LDS image
+  // (LGS_ENC_POST_BATCH; the second pass and WinIn take `batch`).  Its lanes'
+  // validity is not computed here: pmask, pnv and pvm hold it, as the chunk's
+  // interior has it until the loop below changes them near the chunk's end.
+  //   pmask  0xffff in a probe, else 0: the swap's mask.  A lane that is no
+  //          probe has p = 0, so its ds_mskor changes nothing and returns an
+  //          entry of the table, which stands for a position in the chunk:
+  //          its candidate read stays inside the image.  After a match such
+  //          a lane may put back what it received, to the entry it read: the
+  //          lanes that are no probes come after all that are, so nothing
+  //          wrote that entry after it read it, or a probe after the match
+  //          did and the lane received that probe's position, which is past
+  //          the match and not put back.
+  //   pnv    all ones in a lane that must not match (A, and no probes).
+  //   pvm    the lanes that are probes (vmask, and the order note's mask).
+  // B's upper bytes come from lane 5's word: lane l takes lane l + 4's
+  // (row_shl:4; the last four lanes of a row of 16 get 0, and pl.bm is 0
+  // everywhere but in B's lane).
+  constexpr bool kPost = !SERIAL && !IN::kWin && LGS_ENC_POST_BATCH;
+  uint32_t pmask = 0xffffu, pnv = ~pl.vu;
+  uint64_t pvm = ~0ull;
+  Raw32 xi;
+  auto post_batch = [&](uint32_t xv) -> uint64_t {
+    vmask = pvm;
+    h2 = (xv * kHashMul) >> hsh;                                  // snappy.c:44-47
+    ta = h2 & ~3u;
+    const uint32_t sh = (h2 << 3) & 16u;
+    const uint32_t old = lds_mskor_rtn<TAB>(ta, pmask << sh, p << sh);  // snappy.c:146-148
+    prev = vec((old >> sh) & 0xffffu);
+    const Raw32 yr = x.raw32(prev);
+    bad |= ballot(prev > p) & pvm;
+    const uint32_t x4 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)xv, 0x104, 0xf, 0xf, true);
+    const uint32_t w = vec((x4 & pl.bm) | pnv);
+    return ballot(((xv ^ yr.value()) | w) == 0);                  // snappy.c:152
+  };
+  // The copy's end (+ kEndBias) up to which the batch after it has every lane
+  // on (snappy.c:143 for its last lane); never in a chunk shorter than that.
+  const uint32_t amb = n >= kInterior ? n - kInterior + kEndBias : 0u;
   // A probe is on while the probe after it is inside the limit (snappy.c:143):
   // in the batch after a copy, as a bound on the lane's own position.
   const uint32_t lim = last - (pl.e1 - pl.e0);
@@ -672,8 +732,7 @@ __device__ __forceinline__ uint32_t encode_pass(IN& x, uint32_t n, uint16_t* tab
     const uint32_t am_in = am;
     // Rotated: the batch is the loop's last step, so its match test is the
     // loop's only exit (a test in the middle became a selector variable).
-    for (uint64_t mm = batch(evalid); mm;
-         mm = batch((int32_t)p <= (int32_t)lim)) {
+    for (uint64_t mm = batch(evalid); mm;) {
       // ---- the copy (snappy.c:156-169)
       const uint32_t m = (uint32_t)__builtin_ctzll(mm);           // the matching probe
       const uint32_t base = lane_val(p, m);
@@ -684,8 +743,10 @@ __device__ __forceinline__ uint32_t encode_pass(IN& x, uint32_t n, uint16_t* tab
       // LDS atomics serialise where same-address stores do not (as an
       // ds_mskor this store took bank conflicts per launch from 1.0e8 to
       // 2.5e8, profiles/r4b_pmc_mskor_restore.txt).
-      // (Lanes that are no probe have ta at the sink: their received value
-      // is the sink's and must not reach a real entry.)
+      // (After the general batch, lanes that are no probe have ta at the
+      // sink: their received value is the sink's and must not reach a real
+      // entry.  After post_batch such a lane has a real ta and may store
+      // here; it stores the value its entry holds: see pmask at post_batch.)
       *reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(tab) +
                                    (((lane > m) & (prev <= base)) ? (ta | (h2 & 2u)) : kSinkOff)) =
           (uint16_t)prev;
@@ -717,7 +778,7 @@ __device__ __forceinline__ uint32_t encode_pass(IN& x, uint32_t n, uint16_t* tab
       // chunk.
       p = am + pl.e0;
       if constexpr (IN::kWin) x.ensure(am - kEndBias + 1 + kPostLast + 16);
-      xr = x.raw64(p);
+      if constexpr (kPost) xi = x.raw32(p); else xr = x.raw64(p);
       // snappy.c:156 + 166: the literal before the copy (empty after a
       // re-match), then the copy -- recorded, emitted by flush_ops.
       rec_lane(recA, recB, base | (am << 16), ndm, kop);
@@ -725,6 +786,24 @@ __device__ __forceinline__ uint32_t encode_pass(IN& x, uint32_t n, uint16_t* tab
         op = flush_ops(o, op, x, recA, recB, kWave, lit0);
         kop = 0;
         lit0 = am - kEndBias;
+      }
+      if constexpr (kPost) {
+        // (The probe's word before p may change, since the read's own p shifts
+        // it; vec: or the shift is sunk below the branch and p is copied.)
+        const uint32_t xv = vec(xi.value());
+        // Near the chunk's end (and from then on: am only grows) the lanes
+        // past the limit are off.  A branch around this, not a second form
+        // of the batch.
+        if (__builtin_expect(am > amb, 0)) {
+          const bool valid = (int32_t)p <= (int32_t)lim;
+          pvm = ballot(valid);
+          pmask = valid ? 0xffffu : 0u;
+          pnv = ~(valid ? pl.vu : 0u);
+          p = valid ? p : 0u;
+        }
+        mm = post_batch(xv);
+      } else {
+        mm = batch((int32_t)p <= (int32_t)lim);
       }
     }
     if (am - kEndBias >= last) break;

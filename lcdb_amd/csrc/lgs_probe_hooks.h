@@ -12,6 +12,8 @@
 //   LGS_PROBE_DEC_TIMING   decode_kernel: staging, walk and flush cycles
 //                          (tools/dec_phases.py)
 //   LGS_PROBE_FORCE_REPLAY / ENC_TIMING  encode_kernel (tools/enc_phases.py)
+//   LGS_PROBE_ENC_GENERAL_ROUND  encode_pass: the general batch after every
+//                          copy, as before round 13
 //
 // decode_ring_kernel, the kernel decode_pair_kernel replaced, is in the probe
 // library only (lgs_decode_ring.hip: a probe build needs -DLGS_PROBE_DECODERS
@@ -168,6 +170,14 @@ __device__ __forceinline__ uint32_t lgs_hw_where_() {
 #define LGS_ENC_REPLAY(broke) ((broke) | (__builtin_amdgcn_readfirstlane(lgs_enc_second_pass) != 0))
 #else
 #define LGS_ENC_REPLAY(broke) (broke)
+#endif
+// LGS_PROBE_ENC_GENERAL_ROUND: the batch after a copy is the general batch
+// everywhere (validity per lane, lane B's 64-bit compare from a third probe
+// dword), as before round 13; for A/Bs inside one library.
+#ifdef LGS_PROBE_ENC_GENERAL_ROUND
+#define LGS_ENC_POST_BATCH false
+#else
+#define LGS_ENC_POST_BATCH true
 #endif
 #ifdef LGS_PROBE_ENC_TIMING
 #define LGS_ENC_PH_DECL                                                   \
